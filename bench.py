@@ -19,8 +19,10 @@ How N > 1 is launched.  Either form gives N ranks, one per GPU, RCCL (backend "n
     N > torch.cuda.device_count() is an error unless --oversubscribe is given; ranks then share devices and, because RCCL refuses two
     ranks on one device, the control collectives run over gloo on host tensors (reported as "backend" in the line).
 
-One JSON line on rank 0, with "roofline" (dominant kernel = blend backward, live HIP-event duration from the library's
-stage profiler, algorithmic bytes of SURVEY.md §8d) and "cpu_baseline" (the CPU oracle, kind "port", N=1 only).
+One JSON line on rank 0.  A plain run sets up, warms up, times --steps steps (`value`, `ms_per_step`), writes the outputs of two more
+steps on the seeded initial scene if --dump-outputs is given, and prints the line.  With --full the line also carries "roofline" (dominant
+kernel = blend backward, live HIP-event duration from the library's stage profiler, algorithmic bytes of SURVEY.md §8d), the stage times,
+the sync-free and graph-replayed loops, "method_iteration", "cpu_baseline" (the CPU oracle, kind "port", N=1 only) and "parity_full_size".
 """
 import argparse
 import json
@@ -96,13 +98,18 @@ def clock_prewarm(device, ms):
     return (time.perf_counter() - t0) * 1e3
 
 
-def make_step(variant, sc, device):
+LEARNING_RATES = {"means3D": 1.6e-8, "scales": 5e-7, "rotations": 1e-7, "opacities": 1e-6, "shs": 2.5e-6, "colors_precomp": 2.5e-6}
+DUMP_STEPS = 2        # --dump-outputs: steps run on the seeded initial scene; the dumped one is the last (see the comment at the call)
+
+
+def make_step(variant, sc, device, keep_outputs=False):
     """One training iteration.  All gaussian parameters live in ONE flat leaf z (contiguous blocks: means 3P, scales 2P|3P,
     rotations 4P, opacity P, colour 3P|48P), optimised by gsrast.optim.Adam (one fused HIP kernel, include/gsrast.h gsr_adam_step) whose
     per-element `lr_scale` carries the per-group rates of gssr/gaussian/*.setup_optimizers -- one optimizer kernel instead of one per group.
     (GSR_BENCH_TORCH_ADAM=1 selects the earlier form: params = z * lr_scale under torch's fused Adam with lr = 1.)
     The auxiliary-map loss is linear in the 11 (5) channels so autograd hands the rasterizer a dense dL_dothers without
-    materialising one zero-padded [11,H,W] tensor per sliced channel; every gradient path of the backward kernel is live."""
+    materialising one zero-padded [11,H,W] tensor per sliced channel; every gradient path of the backward kernel is live.
+    keep_outputs: every step also keeps what it handed its caller in state["outputs"] (for dump_outputs; the timed steps do not)."""
     from gsrast import runner as hiprun
     import diff_gaussian_rasterization as dgr
     import diff_surfel_rasterization as dsr
@@ -117,8 +124,8 @@ def make_step(variant, sc, device):
     # from the SURVEY 8d distribution the workload is defined on (Adam's step is ~lr per iteration whatever the gradient: with the
     # reference's absolute rates on these post-activation parameters the splat sizes random-walk by +-50 % within 100 steps, and the tile
     # instance count -- hence the work per step -- with them).  The optimiser work per step is the same; config reports R before / after.
-    cols = [("means3D", 3, 1.6e-8), ("scales", ns, 5e-7), ("rotations", 4, 1e-7), ("opacities", 1, 1e-6)]
-    cols.append(("shs", 48, 2.5e-6) if use_sh else ("colors_precomp", 3, 2.5e-6))
+    cols = [("means3D", 3), ("scales", ns), ("rotations", 4), ("opacities", 1), ("shs", 48) if use_sh else ("colors_precomp", 3)]
+    cols = [(k, n, LEARNING_RATES[k]) for k, n in cols]
     # One leaf per parameter tensor, as the reference's models hold them (vanilla_gaussian.py:120-139), every one with its own learning rate;
     # gsrast.optim.Adam updates all of them in ONE launch (gsr_adam_step_multi).  (Rounds 1-2 kept one flat leaf + torch.split, whose backward is a
     # cat of the five gradients: 7 us + a launch gap per iteration; GSR_BENCH_FLAT=1 selects that form, GSR_BENCH_TORCH_ADAM=1 torch's fused Adam on it.)
@@ -175,17 +182,25 @@ def make_step(variant, sc, device):
         if variant == "surfel":
             color, radii, allmap = dsr.GaussianRasterizer(rs)(**kw)
             loss = l1_plus_linear(color, gt, allmap, wmap, root=True)
+            outs = {"allmap": allmap} if keep_outputs else None
         elif variant == "plane":
             color, radii, observe, oam, pd = dpr.GaussianRasterizer(rs)(means2D_abs=m2a, all_map=all_map, **kw)
             loss = l1_plus_linear(color, gt, oam, wmap, root=True) + (pd * wpd).sum()
+            outs = {"observe": observe, "all_map": oam, "plane_depth": pd} if keep_outputs else None
         else:
             color, radii = dgr.GaussianRasterizer(rs)(**kw)
             loss = l1_plus_linear(color, gt, root=True)
+            outs = {} if keep_outputs else None
         loss.backward(gradient=one)
         opt.step()
         opt.zero_grad(set_to_none=True)
         state["viewspace_grad"] = means2D.grad          # what densification reads (viewspace_points.grad[:, :2])
         means2D.grad = None
+        if outs is not None:
+            outs.update(loss=loss, color=color, radii=radii, viewspace_grad=state["viewspace_grad"])
+            if m2a is not None:
+                outs["viewspace_abs_grad"] = m2a.grad
+            state["outputs"] = {k: v.detach() for k, v in outs.items()}
         if m2a is not None:
             m2a.grad = None
         state["vis"] = radii
@@ -201,8 +216,27 @@ def make_step(variant, sc, device):
                 cur[k] = a.reshape(P, 16, 3) if k == "shs" else (a.reshape(P) if k == "opacities" and sc[k].ndim == 1 else a)
         return cur
     state["current_scene"] = current_scene
+    state["param_names"] = [k for k, _, _ in cols]
     state["optimizer"] = opt
     return step, state
+
+
+def dump_outputs(path, state, sample=1 << 20):
+    """--dump-outputs DIR: what a step handed its caller (loss, rasterizer outputs, screen-space gradients: out_<name>.npy) and the
+    parameters as its Adam step left them (param_<name>.npy), float32.  An array of more than `sample` elements is written as the same
+    seeded sample of `sample` of its elements (sorted row-major indices) in every run, so that two builds compare element for element;
+    at most 13 arrays (plane) of at most 4 MiB each."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"out_{k}": v.float().cpu().numpy() for k, v in state["outputs"].items()}
+    cur = state["current_scene"]()
+    arrays.update({f"param_{k}": np.asarray(cur[k], np.float32) for k in state["param_names"]})
+    total = 0
+    for name, a in sorted(arrays.items()):
+        if a.size > sample:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, sample, replace=False))]
+        total += a.nbytes
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, np.float32))
+    assert total <= 64 << 20, total
 
 
 def cpu_baseline(variant, sc, og, budget_s=25.0):
@@ -481,7 +515,16 @@ def main():
                     help="round-1/2 behaviour: all seven stages timed with HIP events inside the timed region (costs ~6 %% of the step in event gaps)")
     ap.add_argument("--no-method-iteration", action="store_true",
                     help="skip the extra 'method_iteration' measurement (full scaffold-2dgs iteration incl. decode, real losses, statistics)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline: stage times and roofline, the sync-free and graph-replayed loops, method_iteration, "
+                         "cpu_baseline and parity_full_size (the --no-* switches above skip parts of it).  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps run DUMP_STEPS steps of the same path on the seeded initial scene and write what the last "
+                         "computed to DIR/<name>.npy (float32; the same inputs in every run; see dump_outputs() and the comment at its call)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.dry_run:
         if "RANK" not in os.environ and args.gpus > 1:
@@ -565,10 +608,11 @@ def main():
     barrier()
     sync_free = rz.static_capacity() if args.sync_free else contextlib.nullcontext()      # (capacity: 1.25 x the running maximum of the warm-up forwards + 16384)
     rz.async_status_reset()
-    # Inside the timed region only the DOMINANT kernel's stage carries HIP events (the live duration behind `roofline`): every timed stage
+    # --full: inside the timed region only the DOMINANT kernel's stage carries HIP events (the live duration behind `roofline`): every timed stage
     # costs two event records = ~10 us of stream idle time per launch (profiles/r03_timeline.json: 82 us of gaps per 1043 us iteration with all
-    # seven stages timed).  The other stages are timed in a second, untimed pass of --stage-steps iterations right after.
-    gsrast.profile_enable(True, stages=None if args.profile_all_stages_in_timed_region else ["blend_bwd"])
+    # seven stages timed).  The other stages are timed in a second, untimed pass of --stage-steps iterations right after.  A plain run times no stage.
+    if args.full:
+        gsrast.profile_enable(True, stages=None if args.profile_all_stages_in_timed_region else ["blend_bwd"])
     t0 = time.perf_counter()
     with sync_free:
         for _ in range(args.steps):
@@ -579,10 +623,53 @@ def main():
         st_async = rz.async_status(reset=True)
         if len(st_async) != args.steps or any(o for _, o, _ in st_async):
             raise SystemExit(f"bench.py --sync-free: {sum(1 for _, o, _ in st_async if o)} of {len(st_async)} forwards overflowed their arena")
-    prof_timed = gsrast.profile_read()
-    gsrast.profile_enable(False)
+    if args.full:
+        prof_timed = gsrast.profile_read()
+        gsrast.profile_enable(False)
     reduce_dev = device if os.environ.get("GSR_BENCH_BACKEND", "nccl") == "nccl" else None
     elapsed, total_iters = tiles.reduce_job(elapsed, args.steps, reduce_dev)
+    if rank == 0 and args.dump_outputs:
+        # Not the state the timed steps left: the blend backward accumulates its gradients with float atomics, whose order (and so the last
+        # bit) varies from run to run, and Adam with eps = 1e-15 turns such differences in near-zero gradients into whole learning-rate
+        # steps; after N + W steps two runs of one command render images that differ by ~2e-5.  DUMP_STEPS steps of the same path on the
+        # seeded initial scene, in the timed loop's --sync-free context, have the same inputs in every run: the last of them carries the
+        # first's Adam moments, step count, screen-space leaves and rasterizer arenas, and its outputs differ between runs by rounding.
+        dump_step, dump_state = make_step(args.variant, sc, device, keep_outputs=True)
+        rz.async_status_reset()
+        with (rz.static_capacity() if args.sync_free else contextlib.nullcontext()):
+            for _ in range(DUMP_STEPS):
+                dump_step()
+        if args.sync_free and any(o for _, o, _ in rz.async_status(reset=True)):
+            raise SystemExit("bench.py --sync-free: a --dump-outputs forward overflowed its arena")
+        dump_outputs(args.dump_outputs, dump_state)
+        del dump_step, dump_state
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "train iters/sec @300k Gaussians 1080p (rasterize fwd+bwd ms and HBM GB/s vs roofline alongside)",
+            "value": round(total_iters / elapsed, 3), "unit": "iters/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "sync_free_forward": bool(args.sync_free), "backend": backend, "dist_world_size": (dist.get_world_size() if dist is not None else 1), "ranks": ranks_seen,
+            "distinct_devices": (len({(r["uuid"], r["pci"]) for r in ranks_seen}) if ranks_seen else 1),
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"diff_{ {'ewa':'gaussian','surfel':'surfel','plane':'plane'}[args.variant] }_rasterization forward+backward "
+                                   f"({ {'ewa':'3DGS EWA','surfel':'2DGS surfel: the rasterizer of configs[1] scaffold-2dgs','plane':'PGSR plane: the rasterizer of configs[2]'}[args.variant] }) "
+                                   f"+ fused L1/linear image loss + fused Adam (gsrast.optim, one HIP kernel) on EXPLICIT Gaussians, {'SH deg 3' if args.color_mode == 'sh' else 'colors_precomp'}, "
+                                   f"P={args.P}, {args.W}x{args.H}, synthetic scene SURVEY §8d (seed=rank); the complete methods (decode, SSIM, "
+                                   f"regularisers, statistics) are timed in method_iteration (--full)",
+                       "variant": args.variant, "P": args.P, "W": args.W, "H": args.H,
+                       "clock_prewarm_ms": round(prewarm_ms, 1),
+                       **({"skew": {"frac": args.skew_frac, "scale": args.skew_scale, "what": "NOT the BASELINE workload: gaussians concentrated at the image centre"}} if args.skew_frac > 0 else {}),
+                       "parallelism": f"{world} independent tile(s), 1 per GPU, no collective"},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     prof = prof_timed
     sync_free_info = None
     if rank == 0 and world == 1 and not args.sync_free:
@@ -673,28 +760,13 @@ def main():
                                       f"{pmc.get('_meta', {}).get('git_revision_of_the_measured_library', 'unrecorded')}) / live avg_launch_ms"}
             except Exception:
                 valu = None
-        out = {
-            "metric": "train iters/sec @300k Gaussians 1080p (rasterize fwd+bwd ms and HBM GB/s vs roofline alongside)",
-            "value": round(total_iters / elapsed, 3), "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "sync_free_forward": bool(args.sync_free), "sync_free": sync_free_info, "backend": backend, "dist_world_size": (dist.get_world_size() if dist is not None else 1), "ranks": ranks_seen,
-            "distinct_devices": (len({(r["uuid"], r["pci"]) for r in ranks_seen}) if ranks_seen else 1),
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"diff_{ {'ewa':'gaussian','surfel':'surfel','plane':'plane'}[args.variant] }_rasterization forward+backward "
-                                   f"({ {'ewa':'3DGS EWA','surfel':'2DGS surfel: the rasterizer of configs[1] scaffold-2dgs','plane':'PGSR plane: the rasterizer of configs[2]'}[args.variant] }) "
-                                   f"+ fused L1/linear image loss + fused Adam (gsrast.optim, one HIP kernel) on EXPLICIT Gaussians, {'SH deg 3' if args.color_mode == 'sh' else 'colors_precomp'}, "
-                                   f"P={args.P}, {args.W}x{args.H}, synthetic scene SURVEY §8d (seed=rank); the complete methods (decode, SSIM, "
-                                   f"regularisers, statistics) are timed in method_iteration",
-                       "variant": args.variant, "P": args.P, "W": args.W, "H": args.H, "tile_instances_R": R, "tile_instances_R_after_timed_steps": R_after,
-                       "visible": int((st["radii"] > 0).sum()),
-                       "clock_prewarm_ms": round(prewarm_ms, 1),
-                       **({"skew": {"frac": args.skew_frac, "scale": args.skew_scale, "what": "NOT the BASELINE workload: gaussians concentrated at the image centre"}} if args.skew_frac > 0 else {}),
-                       "depth_order": "global 4-pass radix sort of the gaussians" if depth_order_is_global(args.P, T, args.variant) else ("per-tile sort of the binned lists, in k_blend_fwd's prologue" if os.environ.get("GSR_TILE_SORT", "fused")[:1] != "k" else "per-tile sort of the binned lists (k_tile_depth_sort)"),
-                       "tiles": T, "tiles_touched": int((st["ranges"][:, 1] > st["ranges"][:, 0]).sum()),
-                       "gaussians_per_tile_mean": round(R / max(int((st["ranges"][:, 1] > st["ranges"][:, 0]).sum()), 1), 1),
-                       "gaussians_per_tile_max": int((st["ranges"][:, 1].astype(np.int64) - st["ranges"][:, 0].astype(np.int64)).max()),
-                       "parallelism": f"{world} independent tile(s), 1 per GPU, no collective"},
+        out["sync_free"] = sync_free_info
+        out["config"].update({"tile_instances_R": R, "tile_instances_R_after_timed_steps": R_after, "visible": int((st["radii"] > 0).sum()),
+                              "depth_order": "global 4-pass radix sort of the gaussians" if depth_order_is_global(args.P, T, args.variant) else ("per-tile sort of the binned lists, in k_blend_fwd's prologue" if os.environ.get("GSR_TILE_SORT", "fused")[:1] != "k" else "per-tile sort of the binned lists (k_tile_depth_sort)"),
+                              "tiles": T, "tiles_touched": int((st["ranges"][:, 1] > st["ranges"][:, 0]).sum()),
+                              "gaussians_per_tile_mean": round(R / max(int((st["ranges"][:, 1] > st["ranges"][:, 0]).sum()), 1), 1),
+                              "gaussians_per_tile_max": int((st["ranges"][:, 1].astype(np.int64) - st["ranges"][:, 0].astype(np.int64)).max())})
+        out.update({
             "rasterize_fwd_ms": round(raster_fwd, 4), "rasterize_bwd_ms": round(raster_bwd, 4),
             "rasterize_fwd_bwd_ms": round(raster_fwd + raster_bwd, 4),
             "stage_ms": {k: round(v, 4) for k, v in ms.items()},
@@ -709,7 +781,7 @@ def main():
                          "algorithmic_bytes_per_launch": int(dom_bytes), "avg_launch_ms": round(ms[dom], 4),
                          "valu_issue": valu,
                          "note": "blend is VALU/atomic-bound by construction (SURVEY §7-5); HBM fraction reported as BASELINE asks"},
-        }
+        })
         try:
             pm = measured_copy_gbs(device)
             out["roofline"].update(peak_measured=round(pm, 1), frac_of_measured=round(achieved / pm, 5),

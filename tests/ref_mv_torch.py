@@ -22,7 +22,7 @@ def _lncc(ref, nea):
 
 
 def multiview_loss(plane_depth, near_plane_depth, normal, distance, gray, near_gray, vc, nc, lambda_geo=0.03, lambda_ncc=0.15, patch=3, th=1.0,
-                   indices=None):
+                   indices=None, aux=None):
     dev = plane_depth.device
     H, W = plane_depth.shape[-2:]
     t = lambda a: torch.as_tensor(a, dtype=torch.float32, device=dev)
@@ -41,6 +41,8 @@ def multiview_loss(plane_depth, near_plane_depth, normal, distance, gray, near_g
     back = ((q - Tn) @ Rn.t()) @ Rv + Tv
     bp = torch.stack([back[:, 0] * vc["Fx"] / back[:, 2] + vc["Cx"], back[:, 1] * vc["Fy"] / back[:, 2] + vc["Cy"]], -1)
     noise = torch.norm(bp - pixels.reshape(-1, 2), dim=-1)
+    if aux is not None:          # per-pixel reprojection error and projection into the neighbour (callers that judge conditioning)
+        aux.update(noise=noise.detach(), proj=proj.detach())
     d_mask = mask & (noise < th)
     weights = (1.0 / torch.exp(noise)).detach()
     weights = torch.where(d_mask, weights, torch.zeros_like(weights))

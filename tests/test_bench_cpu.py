@@ -135,3 +135,25 @@ def test_committed_rocprof_summary_agrees_with_the_bench_line():
     assert line["roofline"]["traffic"] >= line["roofline"]["algorithmic_bytes_per_launch"]
     assert line["metric"].startswith("train iters/sec") and line["unit"] == "iters/s" and line["n_gpus"] == 1 and line["scaling"] == "weak"
     assert {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"])
+
+
+def test_dump_outputs_is_float32_bounded_and_samples_the_same_elements(tmp_path):
+    """--dump-outputs: one float32 .npy per output / parameter; an array above the sample size becomes the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    P, H, W = 1000, 40, 56
+    g = torch.Generator().manual_seed(0)
+    outs = {"loss": torch.tensor(0.5), "color": torch.rand((3, H, W), generator=g), "radii": torch.arange(P, dtype=torch.int32),
+            "allmap": torch.rand((11, H, W), generator=g), "viewspace_grad": torch.rand((P, 3), generator=g)}
+    params = {"means3D": np.random.default_rng(1).random((P, 3)), "opacities": np.random.default_rng(2).random(P)}
+    state = {"outputs": outs, "param_names": list(params), "current_scene": lambda: dict(params, W=W, H=H)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), state, sample=4096)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["out_allmap.npy", "out_color.npy", "out_loss.npy", "out_radii.npy", "out_viewspace_grad.npy", "param_means3D.npy", "param_opacities.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size <= 4096 and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "out_radii.npy"), np.arange(P, dtype=np.float32))
+    assert np.load(tmp_path / "a" / "out_color.npy").shape == (4096,)                # 6720 elements: sampled
+    assert set(np.load(tmp_path / "a" / "out_color.npy")) <= set(outs["color"].numpy().reshape(-1))

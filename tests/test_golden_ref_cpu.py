@@ -139,19 +139,39 @@ def test_plane_multiview_oracle_matches_reference_run():
 
 
 def test_multiview_torch_restatement_matches_reference_run():
-    """tests/ref_mv_torch.py (used for timing and full-size GPU parity) against the same reference-run fixture."""
+    """tests/ref_mv_torch.py (used for timing and full-size GPU parity) against the same reference-run fixture.
+
+    The geometric loss is |reprojected pixel - pixel|: where that distance is below float32 resolution at these pixel coordinates, its
+    gradient is a unit vector whose direction is rounding (the reference's own included; which BLAS kernel the host gets decides it).  The
+    depth gradients are compared without the elements such a pixel feeds: its own plane_depth texel, the four near_plane_depth texels
+    around its projection."""
     import torch
     import ref_mv_torch
     z = golden_ref.load("ref_loss_plane_multiview")
     cam = lambda pre: {k: (z[f"{pre}_{k}"] if k in ("R", "T") else float(z[f"{pre}_{k}"])) for k in ("R", "T", "Fx", "Fy", "Cx", "Cy")}
     lv = {k: torch.tensor(z[k], requires_grad=True) for k in ("plane_depth", "near_plane_depth", "rendered_normal", "rendered_distance")}
+    aux = {}
     geo, ncc = ref_mv_torch.multiview_loss(lv["plane_depth"], lv["near_plane_depth"], lv["rendered_normal"], lv["rendered_distance"],
-                                           torch.tensor(z["gray"]), torch.tensor(z["near_gray"]), cam("v"), cam("n"))
+                                           torch.tensor(z["gray"]), torch.tensor(z["near_gray"]), cam("v"), cam("n"), aux=aux)
     (geo + ncc).backward()
     np.testing.assert_allclose([geo.item(), ncc.item()], [float(z["geo_loss"]), float(z["ncc_loss"])], rtol=1e-5)
+    H, W = lv["plane_depth"].shape[-2:]
+    Hn, Wn = lv["near_plane_depth"].shape[-2:]
+    resolution = 16 * float(np.spacing(np.float32(max(W, H))))                  # a few ulps of a pixel coordinate, accumulated over the chain
+    fragile = np.nonzero(aux["noise"].numpy() < resolution)[0]
+    assert fragile.size <= 1e-2 * H * W, fragile.size
+    skip = {"plane_depth": np.zeros(H * W, bool), "near_plane_depth": np.zeros(Hn * Wn, bool)}
+    skip["plane_depth"][fragile] = True
+    for px, py in aux["proj"].numpy()[fragile]:
+        for y in (int(np.floor(py)), int(np.floor(py)) + 1):
+            for x in (int(np.floor(px)), int(np.floor(px)) + 1):
+                if 0 <= x < Wn and 0 <= y < Hn:
+                    skip["near_plane_depth"][y * Wn + x] = True
     for k in lv:
-        e = z["d_" + k]
-        assert np.linalg.norm(lv[k].grad.numpy() - e) / np.linalg.norm(e) < 1e-4, k
+        got, e = lv[k].grad.numpy().reshape(-1), z["d_" + k].reshape(-1)
+        keep = ~skip[k] if k in skip else np.ones(e.size, bool)
+        assert np.linalg.norm(got[keep] - e[keep]) / np.linalg.norm(e[keep]) < 1e-4, k
+        assert np.isfinite(got).all() and np.abs(got[~keep]).max(initial=0) <= 2 * np.abs(e).max(), k
 
 
 def test_plane_allmap_oracle_matches_reference_run():

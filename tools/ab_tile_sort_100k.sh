@@ -1,5 +1,5 @@
-cd /tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 300 --warmup 20"
+R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp
+B="python $R/bench.py --full --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 300 --warmup 20"
 for r in 1 2; do for v in surfel ewa; do for m in fused kernel; do
 GSR_TILE_SORT=$m $B --variant $v --P 100000 2>/dev/null | tail -1 | python -c "
 import json,sys

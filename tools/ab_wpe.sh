@@ -1,6 +1,6 @@
 # waves per SIMD of the splat-parallel backward (register budget), same box: rebuilds gsr_blend_sp with -DSP_WPE_<V>=n
-cd $GRAFT_REPO_ROOT
-B="python bench.py --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 100 --warmup 10"
+cd "$(dirname "$0")/.."
+B="python bench.py --full --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 100 --warmup 10"
 run() { $B --variant $2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']

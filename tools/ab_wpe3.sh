@@ -1,6 +1,6 @@
 # SURFEL backward: shorter accumulation table + five waves per SIMD, same box
-cd $GRAFT_REPO_ROOT
-B="python bench.py --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 100 --warmup 10"
+cd "$(dirname "$0")/.."
+B="python bench.py --full --no-cpu-baseline --no-method-iteration --no-graph-replay --steps 100 --warmup 10"
 run() { $B 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_ms']

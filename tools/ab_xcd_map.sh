@@ -1,6 +1,6 @@
 # blockIdx -> tile mapping: raster (0) / one band per XCD (1) / 4x4-tile blocks dealt out cyclically (2): it/s, blend times, HBM fetch of the blend kernels
-cd /tmp; export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-method-iteration --no-graph-replay"
+R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp; export TMPDIR=/tmp
+B="python $R/bench.py --full --no-cpu-baseline --no-method-iteration --no-graph-replay"
 for scene in "" "--skew-frac 0.25 --skew-scale 0.3" "--skew-frac 0.5 --skew-scale 0.15"; do for m in 0 1 2; do
 GSR_XCD_REMAP=$m $B --steps 100 --warmup 10 $scene 2>/dev/null | tail -1 | python -c "
 import json,sys

@@ -4,7 +4,7 @@
 # Output under gpurun_out/prof_r02; tools/make_traffic.py r02 turns the PMC passes into profiles/r02_pmc_summary.json + profiles/traffic.json.
 mkdir -p gpurun_out/prof_r02; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r02
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err; echo bench rc=$?
+timeout 900 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo bench rc=$?
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --no-cpu-baseline --no-method-iteration > /dev/null 2>&1; echo stats rc=$?
 B="python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-method-iteration"
 i=0

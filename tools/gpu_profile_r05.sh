@@ -8,8 +8,8 @@
 #   6. BASELINE-size parity report with the float32-geometry floor (tools/full_parity_report.py, 14 cases)
 mkdir -p gpurun_out/prof_r05; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r05
 cd /tmp && export TMPDIR=/tmp
-timeout 1200 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err; echo bench rc=$?
-B="python $R/bench.py --no-cpu-baseline --no-method-iteration --no-graph-replay"
+timeout 1200 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo bench rc=$?
+B="python $R/bench.py --full --no-cpu-baseline --no-method-iteration --no-graph-replay"
 for v in surfel ewa plane; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$v -- $B --variant $v > /dev/null 2>&1; echo stats $v rc=$?
   f=$(find $O/stats_$v -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${v}_kernel_stats.csv

@@ -1,6 +1,6 @@
 # copy the summaries of gpurun_out/prof_r06 (tools/gpu_profile_r06.sh) into profiles/ and stamp the PMC summary with the measured revision:  bash tools/install_profiles.sh
 # Order on the GPU box matters for one pair: bench.py quotes profiles/traffic.json + profiles/r06_pmc_summary.json in its line, so the committed
-# r06_bench_default.json must come from a run made AFTER these two were installed (tools/gpu_profile_r06.sh run twice, or `python bench.py` once more).
+# r06_bench_default.json must come from a run made AFTER these two were installed (tools/gpu_profile_r06.sh run twice, or `python bench.py --full` once more).
 O=gpurun_out/prof_r06; REV=$(git rev-parse --short HEAD)
 for f in bench_default bench_ewa bench_plane bench_ewa_sh; do [ -s $O/$f.json ] && cp $O/$f.json profiles/r06_$f.json; done
 for v in surfel ewa plane; do cp $O/${v}_kernel_stats.csv profiles/r06_${v}_kernel_stats.csv; done

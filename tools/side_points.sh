@@ -1,7 +1,7 @@
 # Side points of §8(d) beside the headline workload, and the bench lines of the other variants:  bash tools/side_points.sh
-# -> gpurun_out/side/{side_points.jsonl, bench_ewa.json, bench_plane.json, bench_ewa_sh.json}
-mkdir -p $GRAFT_REPO_ROOT/gpurun_out/side; O=$GRAFT_REPO_ROOT/gpurun_out/side; cd /tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-method-iteration"
+# -> OUT_DIR (first argument; default $TMPDIR/side): side_points.jsonl, bench_ewa.json, bench_plane.json, bench_ewa_sh.json
+R=$(cd "$(dirname "$0")/.." && pwd); O=${1:-${TMPDIR:-/tmp}/side}; mkdir -p $O; cd /tmp
+B="python $R/bench.py --full --no-cpu-baseline --no-method-iteration"
 $B --variant ewa 2>/dev/null | tail -1 > $O/bench_ewa.json
 $B --variant plane 2>/dev/null | tail -1 > $O/bench_plane.json
 $B --variant ewa --color-mode sh 2>/dev/null | tail -1 > $O/bench_ewa_sh.json
