@@ -3,10 +3,9 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
-
-int gsr_tile_sort_passes(int T);
 
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -75,9 +74,10 @@ static void prof_drain()      // caller holds g_prof_mu
     }
     g_prof.clear();
 }
+// attached: the stage is ONE kernel (the blend backward) whose own dispatch carries the two events -- no event-record packets in front of and behind it
 struct ProfScope {
-    ProfRec r; bool on; hipStream_t s;
-    ProfScope(int label, hipStream_t s_) : on((g_prof_on.load(std::memory_order_relaxed) >> label) & 1u), s(s_)
+    ProfRec r; bool on; hipStream_t s; bool attached;
+    ProfScope(int label, hipStream_t s_, bool attached_ = false) : on((g_prof_on.load(std::memory_order_relaxed) >> label) & 1u), s(s_), attached(attached_)
     {
         if (!on) return;
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -85,12 +85,13 @@ struct ProfScope {
         if (!g_prof_free.empty()) { r = g_prof_free.back(); g_prof_free.pop_back(); }
         else { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); }
         r.label = label;
-        (void)hipEventRecord(r.a, s);
+        if (attached) gsr_blend_bwd_attach_events(r.a, r.b);
+        else (void)hipEventRecord(r.a, s);
     }
     ~ProfScope()
     {
         if (!on) return;
-        (void)hipEventRecord(r.b, s);
+        if (!attached) (void)hipEventRecord(r.b, s);
         std::lock_guard<std::mutex> lk(g_prof_mu);
         g_prof.push_back(r);
     }
@@ -231,6 +232,11 @@ struct Mailbox {
     std::atomic<int> order_ttl{0};          // forwards for which the longest-first launch order stays on after the last long-list report
     std::atomic<int> global_ttl{0};         // forwards for which the global depth order stays on after the last report of a list > 6000 entries
 };
+// One cache line (16 words) per slot -- word 0: num_rendered, word 1: "a gaussian failed the frustum test although prefiltered is set" -- and behind
+// the slots the long-list feedback word.  `base` is Mailbox::host or Mailbox::dev.
+static uint32_t* mail_count(uint32_t* base, unsigned slot) { return base + 16 * slot; }
+static uint32_t* mail_prefiltered(uint32_t* base, unsigned slot) { return base + 16 * slot + 1; }
+static uint32_t* mail_long_list(uint32_t* base) { return base + 16 * GSR_MAIL_SLOTS; }
 static Mailbox g_mail[64];
 static std::mutex g_mail_mu;
 static unsigned take_slot(Mailbox* m)
@@ -251,7 +257,7 @@ static Mailbox* mailbox()
     if (!m.host) {
         void* h = nullptr; void* dp = nullptr;
         if (hipHostMalloc(&h, (GSR_MAIL_SLOTS + 1) * 64, hipHostMallocMapped) != hipSuccess) return nullptr;     // one cache line per slot + the long-list feedback word
-        ((uint32_t*)h)[16 * GSR_MAIL_SLOTS] = 0u;
+        *mail_long_list((uint32_t*)h) = 0u;
         if (hipHostGetDevicePointer(&dp, h, 0) != hipSuccess) { (void)hipHostFree(h); return nullptr; }
         for (int i = 0; i < GSR_MAIL_SLOTS; i++) m.busy[i].store(0);
         m.host = (uint32_t*)h; m.dev = (uint32_t*)dp;
@@ -266,25 +272,44 @@ static Mailbox* mailbox()
 // mapped per-device word when it exceeds max(1024, 4 x mean) (BlendParams::long_word), and the forwards that follow a report -- the next 64 -- run
 // k_tile_order.  The decision costs the host one read of pinned memory; a stale decision is only a slower or faster launch order, never a wrong one
 // (the order's validity travels in the image arena, ImgView::tile_order[T]).  (GSR_TILE_ORDER=0|1 forced it for the round-3/4 A/B runs: removed in round 6.)
-bool gsr_tile_order_wanted()
-{
-    Mailbox* mb = mailbox();
-    return mb && mb->order_ttl.load(std::memory_order_relaxed) > 0;      // set by gsr_decide_depth_order, once per forward
-}
 
-// Once per forward: read the long-list word the previous forwards' blend kernels stored into, refresh the two counters it drives -- longest-first
-// launch order for 64 forwards after a list beyond max(1024, 4 x mean); GLOBAL depth order for 64 forwards after a list beyond 6000 entries, where
-// the prologue's global-memory radix path loses to it (816 vs 780 it/s at 12 633 entries, a tie at 3800: profiles/r03_skewed_density.txt) --
-// and return the depth order of THIS forward.  The caller hands it to every stage launcher; the preprocess kernel records it in the geom arena
-// (GeomView::counters[GSR_CNT_MODE]) for later calls on that arena (gsr_forward_stage2).
-bool gsr_decide_depth_order(const gsr_cfg* cfg)
+// ------------------------------------------------------------------------------------------------ forward plan
+// The environment switches that stay, read ONCE per process (a function-local static: the first use is thread-safe).  GSR_NO_CULL is not among them:
+// gsr_preprocess.hip reads it on every launch.
+struct Switches {
+    int depth_order;       // GSR_DEPTH_ORDER=auto|global|tile: 0 auto (default: gsr_depth_order_static_rule + the long-list feedback), 1 global, 2 tile
+    bool tile_cull;        // GSR_TILE_CULL=0: tiles_touched and the instance list cover the whole tile rect of every gaussian, like the reference's (gsr_tile_cull.h)
+    bool tile_bucket;      // GSR_TILE_BUCKET=0: the two-pass radix sort on the tile id even where the one-pass bucket sort applies (A/B, and the test that
+                           // both leave the same bytes behind the per-tile depth sort)
+};
+static const Switches& switches()
 {
-    const int T = ((cfg->W + GSR_TILE - 1) / GSR_TILE) * ((cfg->H + GSR_TILE - 1) / GSR_TILE);
-    bool forced = false;
-    bool global = gsr_depth_order_static_rule(cfg->P, T, &forced, cfg->variant);
+    static const Switches sw = [] {
+        Switches w;
+        const char* e = getenv("GSR_DEPTH_ORDER"); w.depth_order = !e ? 0 : (e[0] == 'g' ? 1 : (e[0] == 't' ? 2 : 0));
+        e = getenv("GSR_TILE_CULL"); w.tile_cull = e ? atoi(e) != 0 : true;
+        e = getenv("GSR_TILE_BUCKET"); w.tile_bucket = e ? atoi(e) != 0 : true;
+        return w;
+    }();
+    return sw;
+}
+static int tile_count(const gsr_cfg* cfg) { return ((cfg->W + GSR_TILE - 1) / GSR_TILE) * ((cfg->H + GSR_TILE - 1) / GSR_TILE); }
+
+// Stage-1 part of a forward's plan, once per forward: read the long-list word the previous forwards' blend kernels stored into, refresh the two counters
+// it drives -- longest-first launch order for 64 forwards after a list beyond max(1024, 4 x mean); GLOBAL depth order for 64 forwards after a list
+// beyond 6000 entries, where the prologue's global-memory radix path loses to it (816 vs 780 it/s at 12 633 entries, a tie at 3800:
+// profiles/r03_skewed_density.txt) -- and decide the depth order, the tile cull and the launch order of THIS forward.  Nothing else reads the feedback
+// word or writes the counters.  The preprocess kernel records the depth order in the geom arena (GeomView::counters[GSR_CNT_MODE]) for later calls on
+// that arena (gsr_forward_stage2).
+static FwdPlan plan_stage1(const gsr_cfg* cfg)
+{
+    const Switches& sw = switches();
+    FwdPlan plan;
+    plan.global_order = sw.depth_order == 1 || (sw.depth_order == 0 && gsr_depth_order_static_rule(cfg->P, tile_count(cfg), cfg->variant));
+    plan.tile_cull = sw.tile_cull; plan.tile_order = false; plan.bucket_chunk = 0u;
     Mailbox* mb = mailbox();
     if (mb) {
-        volatile uint32_t* w = mb->host + 16 * GSR_MAIL_SLOTS;
+        volatile uint32_t* w = mail_long_list(mb->host);
         const uint32_t longest = *w;
         if (longest != 0u) {
             *w = 0u;
@@ -297,14 +322,36 @@ bool gsr_decide_depth_order(const gsr_cfg* cfg)
             t = mb->global_ttl.load(std::memory_order_relaxed);
             if (t > 0) mb->global_ttl.store(t - 1, std::memory_order_relaxed);
         }
-        if (!forced && mb->global_ttl.load(std::memory_order_relaxed) > 0) global = true;
+        if (sw.depth_order == 0 && mb->global_ttl.load(std::memory_order_relaxed) > 0) plan.global_order = true;
+        plan.tile_order = mb->order_ttl.load(std::memory_order_relaxed) > 0;
     }
-    return global;
+    return plan;
+}
+// FwdPlan::bucket_chunk, once the capacity of the binning arena is known (gsr_common.h: GSR_TB_ROWS_MAX).  Decided on the ARENA's capacity, not on the
+// instance count: every call on that arena gets the same answer.
+static uint32_t gsr_tile_bucket_chunk(bool global_order, int T, uint32_t cap)
+{
+    if (!switches().tile_bucket || global_order || T > GSR_TB_TILES_MAX) return 0u;
+    for (uint32_t chunk = 4096u; chunk <= 16384u; chunk <<= 1)
+        if (gsr_div_up(cap > 0u ? cap : 1u, chunk) <= GSR_TB_ROWS_MAX) return chunk;
+    return 0u;
+}
+// The plan of a gsr_forward_stage2 call: the depth order is the record its stage 1 left (`mode`).  The launch order is the one the counter asks for
+// now -- the stage-1 call refreshed it, and a stage-2 call has no other word from it than that record; a stale answer is only a slower or faster order.
+static FwdPlan plan_stage2(const gsr_cfg* cfg, uint32_t mode, uint32_t cap)
+{
+    FwdPlan plan;
+    plan.global_order = mode == GSR_MODE_GLOBAL;
+    plan.tile_cull = switches().tile_cull;
+    Mailbox* mb = mailbox();
+    plan.tile_order = mb && mb->order_ttl.load(std::memory_order_relaxed) > 0;
+    plan.bucket_chunk = gsr_tile_bucket_chunk(plan.global_order, tile_count(cfg), cap);
+    return plan;
 }
 uint32_t* gsr_long_list_word()
 {
     Mailbox* mb = mailbox();
-    return mb ? mb->dev + 16 * GSR_MAIL_SLOTS : nullptr;
+    return mb ? mail_long_list(mb->dev) : nullptr;
 }
 
 // blockIdx -> tile with 4x4-tile blocks dealt out to the eight XCDs cyclically (workgroup b runs on XCD b % 8): XCD x owns the blocks with
@@ -349,6 +396,26 @@ const uint32_t* gsr_static_tile_map(int gx, int gy, hipStream_t s)
 // the reference's message (auxiliary.h:157); it then traps the device, this library fails the forward call
 #define GSR_PREFILTERED_MSG "Point is filtered although prefiltered is set. This shouldn't happen!"
 
+// ------------------------------------------------------------------------------------------------ arena set-up
+// The three arenas of a call, carved.  The binning arena's layout is always derived from the capacity implied by binning_bytes (forward, backward and
+// debug agree).
+struct Arenas { GeomView g; BinView b; ImgView im; uint32_t cap; };
+#define GSR_UNCHECKED (~(size_t)0)      // geom_bytes / img_bytes: the caller does not check this arena's size
+// need: instances the binning arena must hold; < 0: a speculative forward, any capacity will do (the caller learns of an overflow afterwards)
+static int carve_arenas(const gsr_cfg* cfg, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes, void* img, size_t img_bytes,
+                        long long need, Arenas& a)
+{
+    a.g = gsr_carve_geom(cfg->variant, cfg->P, geom);
+    if (a.g.bytes > geom_bytes) { gsr_set_error("geom buffer too small: %zu < %zu", geom_bytes, a.g.bytes); return 1; }
+    a.cap = gsr_binning_capacity(cfg->variant, binning_bytes, cfg->W, cfg->H);
+    if (need < 0 && a.cap == 0) { gsr_set_error("binning buffer too small"); return 1; }
+    if ((long long)a.cap < need) { gsr_set_error("binning buffer too small: holds %u instances, need %u", a.cap, (uint32_t)need); return 1; }
+    a.b = gsr_carve_bin(cfg->variant, a.cap, cfg->W, cfg->H, binning);
+    a.im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, img);
+    if (a.im.bytes > img_bytes) { gsr_set_error("img buffer too small: %zu < %zu", img_bytes, a.im.bytes); return 1; }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 // cfg->debug (the stream has just been synchronised by gsr_check_launch): did k_duplicate emit what the preprocess kernel counted?
 static int check_cull_agreement(const gsr_cfg* cfg, const GeomView& g, hipStream_t s)
@@ -374,16 +441,16 @@ extern "C" int gsr_forward_stage1_ex(const gsr_cfg* cfg, const gsr_inputs* in, v
     Mailbox* mb = mailbox();
     const unsigned slot = mb ? take_slot(mb) : 0u;
     struct SlotGuard { Mailbox* m; unsigned s; ~SlotGuard() { if (m) release_slot(m, s); } } guard{mb, slot};
-    if (mb) mb->host[16 * slot + 1] = 0u;                      // "a gaussian failed the frustum test although prefiltered is set"
-    const bool global_order = gsr_decide_depth_order(cfg);      // recorded in the geom arena by the preprocess kernel, and handed to the caller for stage 2
-    if (depth_order_host) *depth_order_host = global_order ? GSR_MODE_GLOBAL : GSR_MODE_TILE;
-    { ProfScope ps(GSR_PROF_PREPROCESS, s); if (gsr_launch_preprocess(cfg, in, g, radii, s, global_order, mb ? mb->dev + 16 * slot + 1 : nullptr)) return 1; }
-    { ProfScope ps(GSR_PROF_DEPTH_ORDER, s); if (gsr_launch_depth_order(cfg, g, mb ? mb->dev + 16 * slot : nullptr, s, global_order, true)) return 1; }
+    if (mb) *mail_prefiltered(mb->host, slot) = 0u;
+    const FwdPlan plan = plan_stage1(cfg);      // the depth order is recorded in the geom arena by the preprocess kernel, and handed to the caller for stage 2
+    if (depth_order_host) *depth_order_host = plan.global_order ? GSR_MODE_GLOBAL : GSR_MODE_TILE;
+    { ProfScope ps(GSR_PROF_PREPROCESS, s); if (gsr_launch_preprocess(cfg, in, g, radii, s, plan, mb ? mail_prefiltered(mb->dev, slot) : nullptr)) return 1; }
+    { ProfScope ps(GSR_PROF_DEPTH_ORDER, s); if (gsr_launch_depth_order(cfg, g, mb ? mail_count(mb->dev, slot) : nullptr, s, plan, true)) return 1; }
     // the one host<->device sync of the forward (reference: cudaMemcpy of point_offsets[P-1], rasterizer_impl.cu:281)
     if (mb) {
         GSR_CHECK(hipStreamSynchronize(s), "stage1 sync");
-        *num_rendered_host = *(volatile uint32_t*)(mb->host + 16 * slot);
-        if (cfg->prefiltered && *(volatile uint32_t*)(mb->host + 16 * slot + 1)) { gsr_set_error("%s", GSR_PREFILTERED_MSG); return 1; }
+        *num_rendered_host = *(volatile uint32_t*)mail_count(mb->host, slot);
+        if (cfg->prefiltered && *(volatile uint32_t*)mail_prefiltered(mb->host, slot)) { gsr_set_error("%s", GSR_PREFILTERED_MSG); return 1; }
     } else {
         GSR_CHECK(hipMemcpyAsync(num_rendered_host, g.counters, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "read num_rendered");
         GSR_CHECK(hipStreamSynchronize(s), "stage1 sync");
@@ -403,13 +470,9 @@ extern "C" int gsr_forward_stage2_ex(const gsr_cfg* cfg, const gsr_inputs* in, v
     if (check_cfg(cfg, in)) return 1;
     hipStream_t s = (hipStream_t)stream;
     (void)geom_bytes;
-    GeomView g = gsr_carve_geom(cfg->variant, cfg->P, geom);
-    // the arena layout is always derived from the capacity implied by binning_bytes (forward, backward and debug agree)
-    const uint32_t cap = gsr_binning_capacity(cfg->variant, binning_bytes, cfg->W, cfg->H);
-    if (cap < num_rendered) { gsr_set_error("binning buffer too small: holds %u instances, need %u", cap, num_rendered); return 1; }
-    BinView b = gsr_carve_bin(cfg->variant, cap, cfg->W, cfg->H, binning);
-    ImgView im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, img);
-    if (im.bytes > img_bytes) { gsr_set_error("img buffer too small: %zu < %zu", img_bytes, im.bytes); return 1; }
+    Arenas a;
+    if (carve_arenas(cfg, geom, GSR_UNCHECKED, binning, binning_bytes, img, img_bytes, (long long)num_rendered, a)) return 1;
+    const GeomView& g = a.g;
     if (cfg->P == 0) {
         // the reference returns the zero-initialised outputs untouched when P == 0 (rasterize_points.cu:79-113)
         return 0;
@@ -435,10 +498,10 @@ extern "C" int gsr_forward_stage2_ex(const gsr_cfg* cfg, const gsr_inputs* in, v
         gsr_set_error("geom buffer carries no depth-order record (0x%08x): it must come from gsr_forward_stage1 / gsr_forward of this library, unmodified", mode);
         return 1;
     }
-    const bool global_order = mode == GSR_MODE_GLOBAL;
-    { ProfScope ps(GSR_PROF_BINNING, s); if (gsr_launch_binning(cfg, g, b, im, num_rendered, nullptr, s, global_order)) return 1; }
+    const FwdPlan plan = plan_stage2(cfg, mode, a.cap);
+    { ProfScope ps(GSR_PROF_BINNING, s); if (gsr_launch_binning(cfg, g, a.b, a.im, num_rendered, nullptr, s, plan)) return 1; }
     if (check_cull_agreement(cfg, g, s)) return 1;
-    { ProfScope ps(GSR_PROF_BLEND_FWD, s); if (gsr_launch_blend_fwd(cfg, in, g, b, im, out, s, global_order)) return 1; }
+    { ProfScope ps(GSR_PROF_BLEND_FWD, s); if (gsr_launch_blend_fwd(cfg, in, g, a.b, a.im, out, s, plan)) return 1; }
     return 0;
 }
 extern "C" int gsr_forward_stage2(const gsr_cfg* cfg, const gsr_inputs* in, void* geom, size_t geom_bytes,
@@ -474,28 +537,25 @@ extern "C" int gsr_forward(const gsr_cfg* cfg, const gsr_inputs* in, void* geom,
     if (cfg->P == 0) return 0;
     Mailbox* mb = mailbox();
     if (!mb) { gsr_set_error("gsr_forward: pinned mailbox unavailable, use stage1/stage2"); return 1; }
-    GeomView g = gsr_carve_geom(cfg->variant, cfg->P, geom);
-    if (g.bytes > geom_bytes) { gsr_set_error("geom buffer too small: %zu < %zu", geom_bytes, g.bytes); return 1; }
-    const uint32_t cap = gsr_binning_capacity(cfg->variant, binning_bytes, cfg->W, cfg->H);
-    if (cap == 0) { gsr_set_error("binning buffer too small"); return 1; }
-    BinView b = gsr_carve_bin(cfg->variant, cap, cfg->W, cfg->H, binning);
-    ImgView im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, img);
-    if (im.bytes > img_bytes) { gsr_set_error("img buffer too small: %zu < %zu", img_bytes, im.bytes); return 1; }
+    Arenas a;
+    if (carve_arenas(cfg, geom, geom_bytes, binning, binning_bytes, img, img_bytes, -1, a)) return 1;
+    const GeomView& g = a.g;
     const unsigned slot = take_slot(mb);
     struct SlotGuard { Mailbox* m; unsigned s; ~SlotGuard() { release_slot(m, s); } } guard{mb, slot};
     // How the host learns num_rendered while stage 2 is already queued: k_duplicate (per-tile order) or the scan kernel (global order) stores it into
     // the slot's mapped pinned word (system-scope store) and the host POLLS that word -- preset to a sentinel -- instead of waiting on an event recorded
     // behind stage 1: the event record is a packet of its own and left ~6 us of stream idle time in every forward (profiles/r03_timeline_surfel.json).
     // The poll gives up after 2 s and synchronises the stream instead.
-    volatile uint32_t* word = mb->host + 16 * slot;
-    mb->host[16 * slot + 1] = 0u;                              // "a gaussian failed the frustum test although prefiltered is set"
+    volatile uint32_t* word = mail_count(mb->host, slot);
+    *mail_prefiltered(mb->host, slot) = 0u;
     *word = 0xFFFFFFFFu; std::atomic_thread_fence(std::memory_order_seq_cst);
-    const bool global_order = gsr_decide_depth_order(cfg);
-    { ProfScope ps(GSR_PROF_PREPROCESS, s); if (gsr_launch_preprocess(cfg, in, g, radii, s, global_order, mb->dev + 16 * slot + 1)) return 1; }
-    { ProfScope ps(GSR_PROF_DEPTH_ORDER, s); if (gsr_launch_depth_order(cfg, g, mb->dev + 16 * slot, s, global_order, false)) return 1; }
-    { ProfScope ps(GSR_PROF_BINNING, s); if (gsr_launch_binning(cfg, g, b, im, cap, g.counters, s, global_order, mb->dev + 16 * slot)) return 1; }
+    FwdPlan plan = plan_stage1(cfg);
+    plan.bucket_chunk = gsr_tile_bucket_chunk(plan.global_order, tile_count(cfg), a.cap);
+    { ProfScope ps(GSR_PROF_PREPROCESS, s); if (gsr_launch_preprocess(cfg, in, g, radii, s, plan, mail_prefiltered(mb->dev, slot))) return 1; }
+    { ProfScope ps(GSR_PROF_DEPTH_ORDER, s); if (gsr_launch_depth_order(cfg, g, mail_count(mb->dev, slot), s, plan, false)) return 1; }
+    { ProfScope ps(GSR_PROF_BINNING, s); if (gsr_launch_binning(cfg, g, a.b, a.im, a.cap, g.counters, s, plan, mail_count(mb->dev, slot))) return 1; }
     if (check_cull_agreement(cfg, g, s)) return 1;
-    { ProfScope ps(GSR_PROF_BLEND_FWD, s); if (gsr_launch_blend_fwd(cfg, in, g, b, im, out, s, global_order)) return 1; }
+    { ProfScope ps(GSR_PROF_BLEND_FWD, s); if (gsr_launch_blend_fwd(cfg, in, g, a.b, a.im, out, s, plan)) return 1; }
     uint32_t R;
     {
         const auto t0 = std::chrono::steady_clock::now();
@@ -511,9 +571,9 @@ extern "C" int gsr_forward(const gsr_cfg* cfg, const gsr_inputs* in, void* geom,
         }
     }
     *num_rendered_host = R;
-    *overflow_host = (R > cap) ? 1 : 0;
+    *overflow_host = (R > a.cap) ? 1 : 0;
     // the preprocess has finished by now (num_rendered comes from a kernel behind it), so its word is final
-    if (cfg->prefiltered && *(volatile uint32_t*)(mb->host + 16 * slot + 1)) { gsr_set_error("%s", GSR_PREFILTERED_MSG); return 1; }
+    if (cfg->prefiltered && *(volatile uint32_t*)mail_prefiltered(mb->host, slot)) { gsr_set_error("%s", GSR_PREFILTERED_MSG); return 1; }
     return 0;
 }
 
@@ -529,20 +589,17 @@ extern "C" int gsr_forward_async(const gsr_cfg* cfg, const gsr_inputs* in, void*
     if (cfg->P == 0) { if (gsr_memset_async(status_dev, 0, sizeof(uint32_t), s)) { gsr_set_error("status"); return 1; }; return 0; }
     // cfg->prefiltered: a gaussian that fails the frustum test sets status_dev[2] (sticky, like the overflow word): the reference traps the device
     // (auxiliary.h:156-160), the synchronous forwards fail the call, this one reports it where the caller looks when it synchronises
-    GeomView g = gsr_carve_geom(cfg->variant, cfg->P, geom);
-    if (g.bytes > geom_bytes) { gsr_set_error("geom buffer too small: %zu < %zu", geom_bytes, g.bytes); return 1; }
-    const uint32_t cap = gsr_binning_capacity(cfg->variant, binning_bytes, cfg->W, cfg->H);
-    if (cap == 0) { gsr_set_error("binning buffer too small"); return 1; }
-    BinView b = gsr_carve_bin(cfg->variant, cap, cfg->W, cfg->H, binning);
-    ImgView im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, img);
-    if (im.bytes > img_bytes) { gsr_set_error("img buffer too small: %zu < %zu", img_bytes, im.bytes); return 1; }
-    const bool global_order = gsr_decide_depth_order(cfg);      // a recorded graph replays the decision of its capture
-    if (gsr_launch_preprocess(cfg, in, g, radii, s, global_order, status_dev + 2)) return 1;
-    if (gsr_launch_depth_order(cfg, g, nullptr, s, global_order, false)) return 1;
-    if (gsr_launch_binning(cfg, g, b, im, cap, g.counters, s, global_order, nullptr)) return 1;
+    Arenas a;
+    if (carve_arenas(cfg, geom, geom_bytes, binning, binning_bytes, img, img_bytes, -1, a)) return 1;
+    const GeomView& g = a.g;
+    FwdPlan plan = plan_stage1(cfg);      // a recorded graph replays the plan of its capture
+    plan.bucket_chunk = gsr_tile_bucket_chunk(plan.global_order, tile_count(cfg), a.cap);
+    if (gsr_launch_preprocess(cfg, in, g, radii, s, plan, status_dev + 2)) return 1;
+    if (gsr_launch_depth_order(cfg, g, nullptr, s, plan, false)) return 1;
+    if (gsr_launch_binning(cfg, g, a.b, a.im, a.cap, g.counters, s, plan, nullptr)) return 1;
     // status_dev[0] <- num_rendered, status_dev[1] <- 1 when it exceeds the capacity (sticky: never cleared here): written by the blend forward's
     // first workgroup -- after the binning, whose k_duplicate publishes the total
-    if (gsr_launch_blend_fwd(cfg, in, g, b, im, out, s, global_order, status_dev, cap)) return 1;
+    if (gsr_launch_blend_fwd(cfg, in, g, a.b, a.im, out, s, plan, status_dev, a.cap)) return 1;
     return 0;
 }
 
@@ -560,32 +617,12 @@ extern "C" int gsr_backward_ex(const gsr_cfg* cfg, const gsr_inputs* in, const i
     const size_t need = gsr_backward_scratch_bytes(cfg->variant, cfg->P);
     if (scratch_bytes < need) { gsr_set_error("backward scratch too small: %zu < %zu", scratch_bytes, need); return 1; }
     if (cfg->variant == GSR_PLANE && cfg->render_geo && !og->all_map_pixels) { gsr_set_error("PLANE backward needs all_map_pixels"); return 1; }
-    GeomView g = gsr_carve_geom(cfg->variant, cfg->P, const_cast<void*>(geom));
-    BinView b = gsr_carve_bin(cfg->variant, gsr_binning_capacity(cfg->variant, binning_bytes, cfg->W, cfg->H), cfg->W, cfg->H,
-                              const_cast<void*>(binning));
-    ImgView im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, const_cast<void*>(img));
+    Arenas a;      // the sizes of the forward's arenas are not checked again
+    if (carve_arenas(cfg, const_cast<void*>(geom), GSR_UNCHECKED, const_cast<void*>(binning), binning_bytes, const_cast<void*>(img), GSR_UNCHECKED, 0, a)) return 1;
+    const GeomView& g = a.g;
     float* acc = reinterpret_cast<float*>(scratch);
     if (!(flags & GSR_BWD_SCRATCH_IS_ZERO)) { ProfScope ps(GSR_PROF_BWD_MEMSET, s); if (gsr_memset_async(acc, 0, need, s)) { gsr_set_error("memset acc"); return 1; }; }
-    if (num_rendered > 0) {
-        if (gsr_blend_bwd_is_sp() && ((g_prof_on.load(std::memory_order_relaxed) >> GSR_PROF_BLEND_BWD) & 1u)) {
-            // one kernel: its own dispatch carries the two events (no event-record packets in front of and behind the dominant kernel)
-            ProfRec r;
-            {
-                std::lock_guard<std::mutex> lk(g_prof_mu);
-                if (g_prof.size() >= 8192) prof_drain();
-                if (!g_prof_free.empty()) { r = g_prof_free.back(); g_prof_free.pop_back(); }
-                else { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); }
-            }
-            r.label = GSR_PROF_BLEND_BWD;
-            gsr_blend_bwd_attach_events(r.a, r.b);
-            const int rc = gsr_launch_blend_bwd(cfg, in, g, b, im, og, acc, s);
-            { std::lock_guard<std::mutex> lk(g_prof_mu); g_prof.push_back(r); }
-            if (rc) return 1;
-        } else {
-            ProfScope ps(GSR_PROF_BLEND_BWD, s);
-            if (gsr_launch_blend_bwd(cfg, in, g, b, im, og, acc, s)) return 1;
-        }
-    }
+    if (num_rendered > 0) { ProfScope ps(GSR_PROF_BLEND_BWD, s, true); if (gsr_launch_blend_bwd(cfg, in, g, a.b, a.im, og, acc, s)) return 1; }
     { ProfScope ps(GSR_PROF_PREPROCESS_BWD, s); if (gsr_launch_preprocess_bwd(cfg, in, radii, g, acc, ig, (flags & GSR_BWD_LEAVE_ZERO) != 0, s)) return 1; }
     return 0;
 }

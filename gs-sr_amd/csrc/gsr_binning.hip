@@ -10,9 +10,7 @@
 //   4. tile ranges from key boundaries (identifyTileRanges, rasterizer_impl.cu:116-138).
 // Stability of every pass makes the result identical to the reference's single 64-bit sort.
 #include "gsr_common.h"
-#include "gsr_tile_sort.h"
 #include "gsr_tile_cull.h"
-#include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------ wave helpers
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -353,7 +351,7 @@ __global__ void __launch_bounds__(GSR_SCAN_BLOCK) k_offsets_local(const uint32_t
 }
 // Where the depth order of a tile's list comes from.
 //   "tile" (default, round 3): no global depth sort.  Instances are emitted in ID order, the stable tile sort bins them, and every tile's list is put
-//           in (depth bits, id) order in LDS -- in k_blend_fwd's prologue (gsr_tile_sort.h, GSR_TILE_SORT=fused) or by k_tile_depth_sort (=kernel) --
+//           in (depth bits, id) order in LDS, in k_blend_fwd's prologue (gsr_tile_sort.h),
 //           instead of the eight launches of a 4-pass radix sort over P keys, each of which costs its ~5-10 us latency floor whatever P is
 //           (profiles/r03_timeline_surfel.json).  The block-local prefix of tiles_touched is written by the preprocess kernel, k_duplicate adds up
 //           the block sums in front of its own and publishes num_rendered: no prefix launch at all in the single-call forwards.
@@ -363,24 +361,19 @@ __global__ void __launch_bounds__(GSR_SCAN_BLOCK) k_offsets_local(const uint32_t
 //   P = 600k (337 entries per tile) 0.548 / 0.582;  800k (450) 0.698 / 0.742;  1M (562) 0.878 / 0.889;  1.5M (845) 1.008 / 1.050;
 //   2M (1125) 1.197 / 1.165;  3M (1688) 1.317 / 1.381 -- a tie above ~1.5M (rank by counting is O(n^2) up to 512 entries, a bitonic network above).
 // "auto" (default) takes the per-tile path while P <= 192 tiles' worth of gaussians (1.57M at 1080p).
-// The rule without feedback: GSR_DEPTH_ORDER=global|tile forces one (the returned flag says so), otherwise per tile while P <= 192 T.
-bool gsr_depth_order_static_rule(int P, int T, bool* forced, int variant)
+// The rule of "auto" (GSR_DEPTH_ORDER=global|tile and the long-list feedback override it: gsr_api.hip): per tile while P <= ~192 T.
+bool gsr_depth_order_static_rule(int P, int T, int variant)
 {
-    static int mode = -1;                       // 0 auto, 1 global, 2 tile
-    if (mode < 0) { const char* e = getenv("GSR_DEPTH_ORDER"); mode = !e ? 0 : (e[0] == 'g' ? 1 : (e[0] == 't' ? 2 : 0)); }
-    if (forced) *forced = mode != 0;
-    if (mode == 1) return true;
-    if (mode == 2) return false;
     // the crossover sits at a mean tile list of ~900 entries; an EWA gaussian touches ~5.8 tiles of the SURVEY 8d scene, a PLANE one ~5.1, a surfel ~4.6
     // (EWA at P = 1.5 M, mean 1070: global 640 vs per-tile 609 it/s; surfel at 1.5 M, mean 845: 333 vs 343)
     const long long per_tile = variant == GSR_EWA ? 155ll : (variant == GSR_PLANE ? 176ll : 192ll);
     return (long long)P > per_tile * (long long)T;
 }
 
-int gsr_launch_depth_order(const gsr_cfg* cfg, GeomView g, uint32_t* host_word_dev, hipStream_t s, bool global_order, bool need_total)
+int gsr_launch_depth_order(const gsr_cfg* cfg, GeomView g, uint32_t* host_word_dev, hipStream_t s, const FwdPlan& plan, bool need_total)
 {
     const uint32_t P = (uint32_t)cfg->P;
-    if (!global_order) {
+    if (!plan.global_order) {
         // id order: the block-local prefix and the RAW block sums were written by the preprocess kernel; k_duplicate adds up the sums in front of each
         // workgroup and publishes num_rendered.  A two-stage forward needs the total NOW (the host sizes the binning arena from it): one single-block
         // kernel in its total-only form -- the sums stay raw, so a redo of the binning finds them as the first run did.
@@ -708,189 +701,20 @@ __global__ void __launch_bounds__(1024) k_tile_order(const uint2* __restrict__ r
     if (tid == 0) order[T] = 1u;                  // the order of this forward is in place (k_duplicate cleared the word)
 }
 
-// ------------------------------------------------------------------------------------------------ per-tile depth order
-// One wave per tile: the tile's list (ids in id order after the stable tile sort) is loaded together with the gaussians' depth bits, sorted as
-// 64-bit (depth << 32 | id) words by a bitonic network in the wave's private LDS slice (no barriers: DS operations of a wave execute in order),
-// and the ids are written back.  Lists longer than TDS_WAVE_CAP are left to the end of the workgroup's life, where its four waves sort them
-// together (up to TDS_WG_CAP, block-level network with barriers); anything longer goes through a stable 4-pass LSD radix sort in global
-// memory by the workgroup (scratch: the free ping-pong half of the binning arena) -- slow, correct, and only reached by tiles with > 4096 entries.
-#define TDS_RANK_CAP 256u
-#define TDS_WAVE_CAP 1024u
-#define TDS_WG_CAP 4096u
-// rank-by-counting sort of a list of n <= 64 NQ entries by one wave (see k_tile_depth_sort).  sl: the wave's LDS slice (>= 3 * 64 NQ + 8 dwords).
-// Main loop on the 32-BIT depth keys only (v_cmp_lt_u32 + add: a 64-bit compare issues at a quarter of that rate and made the first version
-// of this kernel compute-bound at 27 us); entries whose keys are equal then collide on their rank, which a per-rank counter in LDS detects,
-// and only then (wave-uniform, rare: two gaussians with bit-identical view depth in one tile) the ranks are recomputed with the id as tie-break.
-template <int NQ>
-__device__ __forceinline__ void tds_rank_sort(unsigned long long* sl64, uint32_t* __restrict__ list, const uint32_t* __restrict__ depth_key, uint32_t n, uint32_t lane)
-{
-    uint32_t* kk = reinterpret_cast<uint32_t*>(sl64);       // [64 NQ + 8] keys, padded with 0xFFFFFFFF (real keys are positive float bits)
-    uint32_t* ii = kk + 64 * NQ + 8;                        // [64 NQ] ids
-    uint32_t* fl = ii + 64 * NQ;                            // [64 NQ] how many entries took each rank
-    uint32_t key[NQ], id[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const uint32_t e = lane + 64u * q;
-        key[q] = 0xFFFFFFFFu; id[q] = 0u;
-        if (e < n) { id[q] = list[e]; key[q] = depth_key[id[q]]; }
-        kk[e] = key[q]; ii[e] = id[q]; fl[e] = 0u;
-    }
-    if (lane < 8u) kk[64u * NQ + lane] = 0xFFFFFFFFu;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    uint32_t rank[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) rank[q] = 0u;
-    for (uint32_t e = 0; e < n; e += 8u) {                   // eight keys per iteration: two independent 16-byte broadcast reads
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = kk[e + u];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            uint32_t c = 0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) c += (v[u] < key[q]) ? 1u : 0u;
-            rank[q] += c;
-        }
-    }
-    bool dup = false;
-#pragma unroll
-    for (int q = 0; q < NQ; q++)
-        if (lane + 64u * q < n) dup |= atomicAdd(&fl[rank[q]], 1u) != 0u;
-    if (__ballot(dup) != 0ull) {                             // some keys are equal: ties go by id (the list arrives in id order, the ids are distinct)
-#pragma unroll
-        for (int q = 0; q < NQ; q++) rank[q] = 0u;
-        for (uint32_t e = 0; e < n; e++) {
-            const uint32_t k2 = kk[e], i2 = ii[e];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) rank[q] += ((k2 < key[q]) | ((k2 == key[q]) & (i2 < id[q]))) ? 1u : 0u;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; q++)
-        if (lane + 64u * q < n) list[rank[q]] = id[q];
-}
-__global__ void __launch_bounds__(256) k_tile_depth_sort(const uint2* __restrict__ ranges, uint32_t T, uint32_t cap, const uint32_t* __restrict__ depth_key,
-                                                         uint32_t* __restrict__ point_list, uint32_t* __restrict__ tile_keys,
-                                                         uint32_t* __restrict__ scratch_keys, uint32_t* __restrict__ scratch_ids, int any_order)
-{
-    __shared__ unsigned long long s_all[TDS_WG_CAP];        // four wave slices of TDS_WAVE_CAP words, or one block-level buffer
-    __shared__ uint32_t s_hist[256], s_cnt[4 * 256], s_lds[17];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t tile = blockIdx.x * 4u + wave;
-    uint2 r = make_uint2(0u, 0u);
-    if (tile < T) r = ranges[tile];
-    r.y = min(r.y, cap);                                     // a speculative forward that overflowed its arena is redone by the caller; stay in bounds
-    const uint32_t n = r.y > r.x ? r.y - r.x : 0u;
-    if (n > 1u && n <= TDS_RANK_CAP) {
-        // short lists (the common case: ~170 entries at 300k gaussians / 1080p): rank by counting.  Every lane holds up to four entries and counts,
-        // over ALL entries of the list (broadcast LDS reads, no dependency between iterations), how many sort in front of each -- the words are
-        // distinct (the id is part of them), so the ranks are a permutation and each id is written straight to its place.  A bitonic network of the
-        // same size is a chain of 36 dependent LDS round trips per wave; this is ~n/2 independent ones.
-        unsigned long long* sl = s_all + wave * TDS_WAVE_CAP;
-        const uint32_t nq = (n + 63u) >> 6;                  // entries per lane actually in use (wave-uniform): 3 for the typical 170-entry list
-        if (nq == 1u) tds_rank_sort<1>(sl, point_list + r.x, depth_key, n, lane);
-        else if (nq == 2u) tds_rank_sort<2>(sl, point_list + r.x, depth_key, n, lane);
-        else if (nq == 3u) tds_rank_sort<3>(sl, point_list + r.x, depth_key, n, lane);
-        else tds_rank_sort<4>(sl, point_list + r.x, depth_key, n, lane);
-    } else if (n > TDS_RANK_CAP && n <= TDS_WAVE_CAP) {
-        unsigned long long* sl = s_all + wave * TDS_WAVE_CAP;
-        uint32_t m = 2u;
-        while (m < n) m <<= 1;
-        for (uint32_t e = lane; e < m; e += 64u) {
-            unsigned long long w = ~0ull;                    // padding sorts behind every real entry
-            if (e < n) { const uint32_t id = point_list[r.x + e]; w = ((unsigned long long)depth_key[id] << 32) | id; }
-            sl[e] = w;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t k = 2u; k <= m; k <<= 1)
-            for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
-                for (uint32_t t = lane; t < (m >> 1); t += 64u) tds_cmpx(sl, t, j, k);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-        for (uint32_t e = lane; e < n; e += 64u) point_list[r.x + e] = (uint32_t)sl[e];
-    }
-    // lists too long for one wave: the workgroup's four waves take them one after the other (block-uniform loop over the four tiles)
-    __shared__ uint32_t s_big[4];
-    if (lane == 0) s_big[wave] = (n > TDS_WAVE_CAP) ? 1u : 0u;
-    __syncthreads();
-    for (uint32_t w4 = 0; w4 < 4u; w4++) {
-        if (!s_big[w4]) continue;                            // block-uniform
-        const uint32_t t4 = blockIdx.x * 4u + w4;
-        uint2 rr = ranges[t4];
-        rr.y = min(rr.y, cap);
-        const uint32_t nn = rr.y - rr.x;
-        __syncthreads();
-        if (nn <= TDS_WG_CAP) {
-            uint32_t m = 2u;
-            while (m < nn) m <<= 1;
-            for (uint32_t e = threadIdx.x; e < m; e += 256u) {
-                unsigned long long w = ~0ull;
-                if (e < nn) { const uint32_t id = point_list[rr.x + e]; w = ((unsigned long long)depth_key[id] << 32) | id; }
-                s_all[e] = w;
-            }
-            __syncthreads();
-            for (uint32_t k = 2u; k <= m; k <<= 1)
-                for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
-                    for (uint32_t t = threadIdx.x; t < (m >> 1); t += 256u) tds_cmpx(s_all, t, j, k);
-                    __syncthreads();
-                }
-            for (uint32_t e = threadIdx.x; e < nn; e += 256u) point_list[rr.x + e] = (uint32_t)s_all[e];
-            __syncthreads();
-        } else {
-            // (keys, ids) = (scratch_keys, point_list) <-> (tile_keys, scratch_ids); tile_keys of this tile is rewritten afterwards (constant = tile id)
-            for (uint32_t e = threadIdx.x; e < nn; e += 256u) scratch_keys[rr.x + e] = depth_key[point_list[rr.x + e]];
-            __threadfence_block();
-            __syncthreads();
-            tds_global_radix(point_list + rr.x, scratch_keys + rr.x, scratch_ids + rr.x, tile_keys + rr.x, nn, s_hist, s_cnt, s_lds, any_order != 0);
-            for (uint32_t e = threadIdx.x; e < nn; e += 256u) tile_keys[rr.x + e] = t4;
-            __syncthreads();
-        }
-    }
-}
-
-// GSR_TILE_CULL=0: tiles_touched and the instance list cover the whole tile rect of every gaussian, like the reference's (gsr_tile_cull.h)
-bool gsr_tile_cull_enabled()
-{
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("GSR_TILE_CULL"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0;
-}
-
-// GSR_TILE_BUCKET=0: the two-pass radix sort on the tile id even where the one-pass bucket sort applies (A/B, and the test that both leave the same
-// bytes behind the per-tile depth sort).
-uint32_t gsr_tile_bucket_chunk(bool global_order, int T, uint32_t cap)
-{
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("GSR_TILE_BUCKET"); on = e ? (atoi(e) != 0) : 1; }
-    if (!on || global_order || T > GSR_TB_TILES_MAX) return 0u;
-    for (uint32_t chunk = 4096u; chunk <= 16384u; chunk <<= 1)
-        if (gsr_div_up(cap > 0u ? cap : 1u, chunk) <= GSR_TB_ROWS_MAX) return chunk;
-    return 0u;
-}
-
-// GSR_TILE_SORT=fused (default): k_blend_fwd orders its tile's list in its prologue (gsr_tile_sort.h); =kernel: the separate k_tile_depth_sort launch.
-bool gsr_tile_sort_is_fused()
-{
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("GSR_TILE_SORT"); fused = (e && e[0] == 'k') ? 0 : 1; }
-    return fused != 0;
-}
-
+// ------------------------------------------------------------------------------------------------ binning
 static int tile_bits(int T)
 {
     int b = 1;
     while ((1 << b) < T) b++;
     return b;
 }
-int gsr_tile_sort_passes(int T) { return (tile_bits(T) + 7) / 8; }
 
 // R is the exact instance count, or -- when n_dev != nullptr -- the CAPACITY of the binning arena while the exact count
 // is read on the device from *n_dev (speculative forward: the host has not seen it yet).
 int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, uint32_t R, const uint32_t* n_dev, hipStream_t s,
-                       bool global_order, uint32_t* host_word_dev)
+                       const FwdPlan& plan, uint32_t* host_word_dev)
 {
+    const bool global_order = plan.global_order;
     const int gx = (cfg->W + GSR_TILE - 1) / GSR_TILE, gy = (cfg->H + GSR_TILE - 1) / GSR_TILE;
     const int T = gx * gy;
     if (R == 0) {
@@ -900,7 +724,7 @@ int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, ui
         return 0;
     }
     // unsorted instances go to the buffer from which an integral number of passes lands in (tile_keys, point_list)
-    const int passes = gsr_tile_sort_passes(T);
+    const int passes = (tile_bits(T) + 7) / 8;
     uint32_t *k0 = (passes & 1) ? b.keys_b : b.tile_keys, *v0 = (passes & 1) ? b.vals_b : b.point_list;
     uint32_t *k1 = (passes & 1) ? b.tile_keys : b.keys_b, *v1 = (passes & 1) ? b.point_list : b.vals_b;
     // 4096-key blocks for the tile sort from this many instances on, 1024-key blocks below (the threshold was an environment switch while it was being measured).  Re-measured at the end of
@@ -909,7 +733,7 @@ int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, ui
     const uint32_t big_from0 = 1700000u;
     // R is the CAPACITY of the arena when the count is read on the device (speculative / sync-free forwards: 1.25 x the last count + 16384)
     const uint32_t big_from = n_dev ? big_from0 + big_from0 / 4 : big_from0;
-    const uint32_t chunk = gsr_tile_bucket_chunk(global_order, T, b.cap);         // decided on the arena's capacity: the blend forward decides the same way
+    const uint32_t chunk = plan.bucket_chunk;
     const bool bucket = chunk != 0u;
     if (bucket) { k0 = b.keys_b; v0 = b.vals_b; }                               // emission order -> (keys_b, vals_b); BinView::tile_keys is not written
     {
@@ -923,7 +747,7 @@ int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, ui
         const uint32_t snb = global_order ? 0u : gsr_div_up((uint32_t)cfg->P, 256u);
 #define GSR_DUP(CV) hipLaunchKernelGGL(k_duplicate<CV>, dg, db, 0, s, (uint32_t)cfg->P, sidx, g.offsets, g.scan_tmp, g.tiles_touched, g.rect, g.cull, gx, k0, v0, R, \
                                        im.ranges, (uint32_t)T, zp, zn, im.tile_order + T, sblk, snb, g.counters, host_word_dev)
-        if (!gsr_tile_cull_enabled()) GSR_DUP(-1);
+        if (!plan.tile_cull) GSR_DUP(-1);
         else if (cfg->variant == GSR_SURFEL) GSR_DUP(GSR_SURFEL);
         else GSR_DUP(GSR_EWA);
 #undef GSR_DUP
@@ -938,19 +762,13 @@ int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, ui
         hipLaunchKernelGGL((k_tb_scatter<TH>), dim3(rows), dim3(TH), lds_h, s, k0, v0, R, n_dev, Tp, b.tile_tab, b.point_list); } while (0)
         if (chunk == 4096u) GSR_TB(256); else if (chunk == 8192u) GSR_TB(512); else GSR_TB(1024);
 #undef GSR_TB
-        if (!gsr_tile_sort_is_fused())
-            hipLaunchKernelGGL(k_tile_depth_sort, dim3(gsr_div_up((uint32_t)T, 4u)), dim3(256), 0, s, im.ranges, (uint32_t)T, R, g.depth_key, b.point_list, b.tile_keys,
-                               b.keys_b, b.vals_b, 1);
-        if (gsr_tile_order_wanted()) hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, im.ranges, (uint32_t)T, im.tile_order);
+        if (plan.tile_order) hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, im.ranges, (uint32_t)T, im.tile_order);
         return gsr_check_launch("binning", s, cfg->debug);
     }
     bool in_b = false;
     // (tile ranges written by the last scatter pass instead of k_tile_ranges were measured in round 3 and lost: binning 0.0847 vs 0.0748 ms, DESIGN Appendix A (42))
     if (gsr_radix_sort_pairs(k0, v0, k1, v1, R, n_dev, 0, tile_bits(T), 8, false, b.hist, &in_b, s, R >= big_from, true)) return 1;
     hipLaunchKernelGGL(k_tile_ranges, dim3(gsr_div_up(R, 256)), dim3(256), 0, s, R, n_dev, b.tile_keys, im.ranges);
-    if (!global_order && !gsr_tile_sort_is_fused())
-        hipLaunchKernelGGL(k_tile_depth_sort, dim3(gsr_div_up((uint32_t)T, 4u)), dim3(256), 0, s, im.ranges, (uint32_t)T, R, g.depth_key, b.point_list, b.tile_keys,
-                           b.keys_b, b.vals_b, 0);
-    if (gsr_tile_order_wanted()) hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, im.ranges, (uint32_t)T, im.tile_order);
+    if (plan.tile_order) hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, im.ranges, (uint32_t)T, im.tile_order);
     return gsr_check_launch("binning", s, cfg->debug);
 }

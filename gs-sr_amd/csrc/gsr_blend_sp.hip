@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(256) SP_OCC k_blend_bwd_sp(BlendParams p)
     constexpr int PCW = 64, PCR = 16;
     __shared__ float4 s_pc[NC4 > 0 ? 4 * PCW * NC4 : 1];    // [wave][row][pixel]: the per-pixel multiplicands the steps fetch from LDS (SpTraits::NC4)
 
-    const int tile = tile_of_block(blockIdx.x, p.gx * p.gy, p.xcd_remap, p.tile_order, p.static_map);
+    const int tile = tile_of_block(blockIdx.x, p.gx * p.gy, p.tile_order, p.static_map);
     const int tx = tile % p.gx, ty = tile / p.gx;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = lane >> 4, j = lane & 15;                 // row (= 4x4 block of the quadrant), slot / pixel inside it
@@ -693,7 +693,7 @@ __global__ void __launch_bounds__(256) SP_OCC k_blend_bwd_sp(BlendParams p)
 // An event record is a barrier packet of its own: ~6 us of stream idle time each, on both sides of the kernel it measures
 // (profiles/r03_timeline_surfel.json) -- 1.3 % of the iteration bench.py times with this stage's profiling on.  Thread-local, consumed by the next launch.
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
-void gsr_blend_bwd_sp_attach_events(hipEvent_t start, hipEvent_t stop) { t_ev_start = start; t_ev_stop = stop; }
+void gsr_blend_bwd_attach_events(hipEvent_t start, hipEvent_t stop) { t_ev_start = start; t_ev_stop = stop; }
 
 int gsr_launch_blend_bwd_sp(const BlendParams& p, int variant, hipStream_t s)
 {

@@ -102,10 +102,18 @@ int gsr_check_launch(const char* what, hipStream_t s, bool debug);
     } while (0)
 
 // ---- stage launchers (each in its own .hip) ------------------------------------------------------------------
-// Depth order of a forward (global stable sort of the gaussians by depth, or every tile's list sorted in the blend forward's prologue): decided ONCE
-// per forward by its entry point (gsr_decide_depth_order, gsr_api.hip) and handed to every stage launcher as `global_order`.  It also fixes the layout of
-// offsets / scan_tmp / sorted_idx in the geom arena, so the preprocess kernel records it IN the arena (GeomView::counters[GSR_CNT_MODE]); a later call
-// on that arena (gsr_forward_stage2, also the redo after an overflowed gsr_forward) reads it back and refuses an arena that carries none.
+// How ONE forward runs: filled once by its entry point (gsr_api.hip, the only reader of the GSR_* switches and of the long-list feedback) and handed to
+// every stage launcher, which derives nothing of its own.  The backward has no plan: it reads the lists the forward left.
+struct FwdPlan {
+    bool global_order;        // depth order: global stable sort of the gaussians by depth, or every tile's list sorted in the blend forward's prologue.  It fixes
+                              // the layout of offsets / scan_tmp / sorted_idx in the geom arena, so the preprocess kernel records it IN the arena
+                              // (GeomView::counters[GSR_CNT_MODE]); a later call on that arena (gsr_forward_stage2, also the redo after an overflowed
+                              // gsr_forward) reads the record back and refuses an arena that carries none
+    bool tile_cull;           // tile instances culled at emission (gsr_tile_cull.h): the preprocess kernel counts what k_duplicate emits, instance for instance
+    bool tile_order;          // k_tile_order runs: the blend workgroups take the tiles longest list first
+    uint32_t bucket_chunk;    // instances per chunk of the one-pass bucket sort on the tile id, 0: the two-pass radix sort.  Filled once the binning arena's
+                              // capacity is known (stage 2); the preprocess and the depth order do not look at it
+};
 #define GSR_CNT_MODE 1
 // counters[GSR_CNT_CULL_MISMATCH]: set by k_duplicate when a wave emitted a different number of instances than its gaussians counted in the preprocess kernel
 // (both run gsr_tile_cull.h's test on the same words; a disagreement would shift every later instance of the list).  Cleared by the preprocess kernel, looked
@@ -113,32 +121,24 @@ int gsr_check_launch(const char* what, hipStream_t s, bool debug);
 #define GSR_CNT_CULL_MISMATCH 2
 #define GSR_MODE_TILE 0x47530001u
 #define GSR_MODE_GLOBAL 0x47530002u
-bool gsr_decide_depth_order(const gsr_cfg* cfg);          // static rule (GSR_DEPTH_ORDER, P <= ~192 T) + the long-list feedback; polls the feedback word: call once per forward
-int gsr_launch_preprocess(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, int32_t* radii, hipStream_t s, bool global_order, uint32_t* prefiltered_err = nullptr);
+int gsr_launch_preprocess(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, int32_t* radii, hipStream_t s, const FwdPlan& plan, uint32_t* prefiltered_err = nullptr);
 // global order: sorted_idx, offsets, the scanned block sums and counters[0]; per-tile order: nothing unless `need_total` (two-stage forward: the host
 // sizes the binning arena from num_rendered) -- otherwise k_duplicate adds up the raw block sums and publishes the total itself
-int gsr_launch_depth_order(const gsr_cfg* cfg, GeomView g, uint32_t* host_word_dev, hipStream_t s, bool global_order, bool need_total);
+int gsr_launch_depth_order(const gsr_cfg* cfg, GeomView g, uint32_t* host_word_dev, hipStream_t s, const FwdPlan& plan, bool need_total);
 int gsr_launch_binning(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im, uint32_t R, const uint32_t* n_dev, hipStream_t s,
-                       bool global_order, uint32_t* host_word_dev = nullptr);
+                       const FwdPlan& plan, uint32_t* host_word_dev = nullptr);
 int gsr_launch_blend_fwd(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, BinView b, ImgView im,
-                         const gsr_outputs* out, hipStream_t s, bool global_order, uint32_t* status_dev = nullptr, uint32_t status_cap = 0u);
+                         const gsr_outputs* out, hipStream_t s, const FwdPlan& plan, uint32_t* status_dev = nullptr, uint32_t status_cap = 0u);
 int gsr_launch_blend_bwd(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, BinView b, ImgView im,
                          const gsr_out_grads* og, float* acc, hipStream_t s);
-bool gsr_blend_bwd_is_sp();            // GSR_BWD=sp (default) | px (gsr_blend.hip)
-void gsr_blend_bwd_attach_events(hipEvent_t start, hipEvent_t stop);     // splat-parallel backward only: the next launch of this thread carries them
-// hipMemsetAsync that is safe to record into a HIP graph: on ROCm 7.2 a memset NODE replays with a corrupted fill value from the second replay
-// on (measured round 3: vis_idx filled with 0x5A5A5A5A instead of 0xFF...), so while `s` is being captured the fill is a kernel; eagerly it is
-// the runtime's memset.  nbytes must be a multiple of 4.
-bool gsr_depth_order_static_rule(int P, int T, bool* forced, int variant = GSR_SURFEL);   // GSR_DEPTH_ORDER=tile|global|auto and the P <= 192 T rule (gsr_binning.hip)
-bool gsr_tile_cull_enabled();         // GSR_TILE_CULL=0|1 (default 1): tile instances culled at emission (gsr_tile_cull.h, gsr_binning.hip)
+void gsr_blend_bwd_attach_events(hipEvent_t start, hipEvent_t stop);     // the next gsr_launch_blend_bwd of this thread carries them on its dispatch (gsr_blend_sp.hip)
+bool gsr_depth_order_static_rule(int P, int T, int variant);            // GSR_DEPTH_ORDER=auto: global above ~192 gaussians per tile (gsr_binning.hip)
 // One-pass bucket sort on the tile id (per-tile depth order only: it leaves a tile's list in no particular order, which the sort by (depth, id) that
 // follows does not mind).  Chunks of 4096 / 8192 / 16384 instances (the smallest that keeps the arena's capacity within GSR_TB_ROWS_MAX chunks: more
 // workgroups for the scattered stores), a table of per-(chunk, tile) counts; applies up to GSR_TB_TILES_MAX tiles (the 16-bit counters of two tiles
-// share an LDS word) and GSR_TB_ROWS_MAX chunks of 16384, else the two-pass radix sort.  GSR_TILE_BUCKET=0: never.
+// share an LDS word) and GSR_TB_ROWS_MAX chunks of 16384, else the two-pass radix sort (FwdPlan::bucket_chunk, gsr_api.hip).  GSR_TILE_BUCKET=0: never.
 #define GSR_TB_ROWS_MAX 256u
 #define GSR_TB_TILES_MAX 16384
-// -> instances per chunk (0: the bucket sort does not apply).  Decided on the ARENA's capacity, so that binning and blend forward agree.
-uint32_t gsr_tile_bucket_chunk(bool global_order, int T, uint32_t cap);
 static inline size_t gsr_tile_bucket_words(uint32_t cap, size_t T)
 {
     if (T > (size_t)GSR_TB_TILES_MAX) return 0;
@@ -147,10 +147,11 @@ static inline size_t gsr_tile_bucket_words(uint32_t cap, size_t T)
 }
 #define GSR_TB_GROUPS_MAX (GSR_TB_TILES_MAX / 64)       // behind the table (BinView::tile_tab + gsr_tile_bucket_words(cap, T)): per chunk, the exclusive prefix of its
                                                         // instances over the groups of 64 tiles, [GSR_TB_ROWS_MAX][GSR_TB_GROUPS_MAX]
-bool gsr_tile_sort_is_fused();        // GSR_TILE_SORT=fused|kernel: who orders a tile's list by depth when the depth order is per tile (gsr_binning.hip)
-bool gsr_tile_order_wanted();         // on while recent forwards reported long tile lists (gsr_api.hip); once per forward
 const uint32_t* gsr_static_tile_map(int gx, int gy, hipStream_t s);     // device [gx*gy] blockIdx -> tile, block-cyclic over the XCDs; cached per device and grid; nullptr if unavailable (gsr_api.hip)
 uint32_t* gsr_long_list_word();       // device pointer of the per-device feedback word the blend forward reports long lists into, or nullptr (gsr_api.hip)
+// hipMemsetAsync that is safe to record into a HIP graph: on ROCm 7.2 a memset NODE replays with a corrupted fill value from the second replay
+// on (measured round 3: vis_idx filled with 0x5A5A5A5A instead of 0xFF...), so while `s` is being captured the fill is a kernel; eagerly it is
+// the runtime's memset.  nbytes must be a multiple of 4.
 int gsr_memset_async(void* p, int byte_value, size_t nbytes, hipStream_t s);
 int gsr_launch_preprocess_bwd(const gsr_cfg* cfg, const gsr_inputs* in, const int32_t* radii, GeomView g,
                               float* acc, const gsr_in_grads* ig, bool leave_zero, hipStream_t s);

@@ -401,18 +401,22 @@ static PreParams make_params(const gsr_cfg* cfg, const gsr_inputs* in, GeomView 
     p.means3D = in->means3D; p.shs = in->shs; p.colors = in->colors_precomp; p.opac = in->opacities;
     p.scales = in->scales; p.rots = in->rotations; p.cov3D_pre = in->cov3D_precomp; p.all_map = in->all_map;
     p.view = cfg->viewmatrix; p.proj = cfg->projmatrix; p.campos = cfg->campos;
+    // read on EVERY launch, unlike the switches of gsr_api.hip: the neutrality test of the sub-tile cull sets it between two forwards of one process,
+    // and a cached read would have it compare a culled run with a culled run
     { const char* e = getenv("GSR_NO_CULL"); p.no_cull = (e && atoi(e) != 0) ? 1 : 0; }
     p.in_mask = nullptr; p.scale_stride = 3;
     p.scan_offsets = nullptr; p.scan_sums = nullptr; p.prefiltered_err = nullptr; p.mode_word = nullptr; p.mode = 0u;
-    p.tile_cull = gsr_tile_cull_enabled() ? 1 : 0;
+    p.tile_cull = 0;
     p.radii = radii; p.g = g;
     p.zero_ptr = nullptr; p.zero_n = 0;
     return p;
 }
 
-int gsr_launch_preprocess(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, int32_t* radii, hipStream_t s, bool global_order, uint32_t* prefiltered_err)
+int gsr_launch_preprocess(const gsr_cfg* cfg, const gsr_inputs* in, GeomView g, int32_t* radii, hipStream_t s, const FwdPlan& plan, uint32_t* prefiltered_err)
 {
+    const bool global_order = plan.global_order;
     PreParams p = make_params(cfg, in, g, radii);
+    p.tile_cull = plan.tile_cull ? 1 : 0;
     p.prefiltered_err = cfg->prefiltered ? prefiltered_err : nullptr;
     p.zero_ptr = g.hist; p.zero_n = global_order ? gsr_sort_group_words((uint32_t)cfg->P, false, 256) : 0u;      // first group histogram of the global depth sort
     p.mode_word = g.counters + GSR_CNT_MODE; p.mode = global_order ? GSR_MODE_GLOBAL : GSR_MODE_TILE;

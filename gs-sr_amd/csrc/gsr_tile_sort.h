@@ -1,11 +1,9 @@
 // gsr_tile_sort.h -- order ONE tile's list by (depth bits, gaussian id), all 256 threads of a workgroup together.
 //
 // The reference's single 64-bit radix sort (3DGS rasterizer_impl.cu:300-308: key = tile << 32 | depth bits, stable => ties by gaussian id) is
-// reproduced here per tile, after a sort on the tile id alone has grouped the instances (gsr_binning.hip).  Two callers:
-//   * k_blend_fwd (gsr_blend.hip), as its prologue: the sort's dependent loads (ids -> depth keys) hide behind the blending of the
-//     other resident tiles instead of being a latency-bound launch of their own (GSR_TILE_SORT=fused, default);
-//   * k_tile_depth_sort (gsr_binning.hip), one WAVE per tile for short lists (GSR_TILE_SORT=kernel: the round-3 form, kept for A/B).
-// Both leave the same bytes in point_list.
+// reproduced here per tile, after a sort on the tile id alone has grouped the instances (gsr_binning.hip), by k_blend_fwd (gsr_blend.hip) as its
+// prologue: the sort's dependent loads (ids -> depth keys) hide behind the blending of the other resident tiles instead of being a latency-bound
+// launch of their own.  (A stand-alone kernel, one wave per tile, did this in round 3; slower at every size but 100k gaussians, removed in round 7.)
 #pragma once
 #include "gsr_common.h"
 

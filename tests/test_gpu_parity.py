@@ -671,8 +671,8 @@ def test_equal_depths_tie_by_id(variant):
 @pytest.mark.parametrize("variant,P", [("ewa", 700), ("surfel", 1500), ("plane", 2200), ("surfel", 5000), ("plane", 9000), ("ewa", 40000), ("surfel", 24000)])
 def test_long_tile_lists_sort_paths(variant, P, monkeypatch):
     """(GSR_DEPTH_ORDER=tile unless the environment already chose: "auto" would send these gaussian counts to the global sort.)  A 48x32 image (6 tiles) with thousands of gaussians per tile: the per-tile depth sort's paths -- rank by counting (<= 256 entries), the LDS
-    bitonic network (fused: <= 1024 entries EWA / 2048 PLANE, SURFEL, the forward's staging LDS; kernel: one wave <= 1024, the workgroup <= 4096) and
-    the global-memory radix fallback (longer) -- give the oracle's list bit for bit, and the
+    bitonic network (<= 2048 entries, the forward's staging LDS) and
+    the global-memory radix fallback (longer) of the blend forward's prologue -- give the oracle's list bit for bit, and the
     tile keys survive the fallback's use of their array as scratch."""
     hr = _hiprun()
     if "GSR_DEPTH_ORDER" not in os.environ:
@@ -704,20 +704,20 @@ def test_tile_count_edges_of_the_bucket_sort(W, H, what):
         assert np.array_equal(st["radii"], f.radii)
 
 
-# The switches that stay in the product, each read once per process, so every set runs in a child process; orthogonal switches share a child (round 4 spent
+# The switches that stay in the product, read once per process, so every set runs in a child process; orthogonal switches share a child (round 4 spent
 # eight child processes on them):
-#   A  the reference-shaped paths: GSR_BWD=px (round 1's pixel-parallel backward), GSR_DEPTH_ORDER=global (rounds 1-2's global LSD sort of the gaussians),
-#      GSR_TILE_CULL=0 (every tile of every rect emitted: R, tiles_touched, point_list, tile keys and ranges bit-exact against the oracle's, see
-#      test_forward_backward_parity), GSR_XCD_REMAP=0 (raster launch order);
-#   B  GSR_DEPTH_ORDER=tile forced + GSR_TILE_SORT=kernel (the per-tile sort as its own launch), GSR_TILE_BUCKET=0 (two radix passes on the tile id: real tile
-#      keys, so `ranges` is held against keys the bucket sort's debug view would have rebuilt from it), GSR_XCD_REMAP=1 (banded launch order);
-#   C  GSR_DEPTH_ORDER=tile forced + GSR_TILE_SORT=fused: the long-list paths of the blend forward's prologue.
+#   A  the reference-shaped paths: GSR_DEPTH_ORDER=global (rounds 1-2's global LSD sort of the gaussians) and GSR_TILE_CULL=0 (every tile of every rect
+#      emitted: R, tiles_touched, point_list, tile keys and ranges bit-exact against the oracle's, see test_forward_backward_parity); the backward reads
+#      the unculled lists;
+#   B  GSR_DEPTH_ORDER=tile forced + GSR_TILE_BUCKET=0 (two radix passes on the tile id: real tile keys, so `ranges` is held against keys the bucket
+#      sort's debug view would have rebuilt from it);
+#   C  GSR_DEPTH_ORDER=tile forced, bucket sort on: the long-list paths of the blend forward's prologue on lists that arrive in no particular order.
 SWITCH_SETS = {
-    "A": (dict(GSR_BWD="px", GSR_DEPTH_ORDER="global", GSR_TILE_CULL="0", GSR_XCD_REMAP="0"),
+    "A": (dict(GSR_DEPTH_ORDER="global", GSR_TILE_CULL="0"),
           "test_forward_backward_parity or test_edge_cases or test_long_tile_lists or test_speculative_forward or test_full_size_properties"),
-    "B": (dict(GSR_DEPTH_ORDER="tile", GSR_TILE_SORT="kernel", GSR_TILE_BUCKET="0", GSR_XCD_REMAP="1"),
+    "B": (dict(GSR_DEPTH_ORDER="tile", GSR_TILE_BUCKET="0"),
           "test_forward_backward_parity or test_edge_cases or test_long_tile_lists or test_equal_depths or test_speculative_forward or test_full_size_properties"),
-    "C": (dict(GSR_DEPTH_ORDER="tile", GSR_TILE_SORT="fused"), "test_long_tile_lists or test_equal_depths or test_forward_backward_parity"),
+    "C": (dict(GSR_DEPTH_ORDER="tile"), "test_long_tile_lists or test_equal_depths or test_forward_backward_parity"),
 }
 
 
