@@ -267,10 +267,12 @@ __device__ __forceinline__ void load_xb(const DecArgs& p, int a, bool active, in
     dist = sqrtf(r0 * r0 + r1 * r1 + r2 * r2);
     vw[0] = r0 / dist; vw[1] = r1 / dist; vw[2] = r2 / dist;
     const float lv = p.in.level ? p.in.level[a] : 0.0f;
-    const float am = active ? 1.0f : 0.0f;
-    xb[0] = (f32x4){f0.x, f0.y, f0.z, f0.w} * am;
-    xb[1] = (f32x4){f1.x, f1.y, f1.z, f1.w} * am;
-    xb[2] = (kk == 0 ? (f32x4){vw[0], vw[1], vw[2], dist} : (kk == 1 ? (f32x4){lv, 1.0f, 0.0f, 0.0f} : (f32x4){0.f, 0.f, 0.f, 0.f})) * am;
+    // inactive rows read anchor 0, which need not be finite (at the camera centre its view vector is 0/0): SELECT zeros, never multiply by 0 -- a NaN
+    // column in the scratch poisons the weight-gradient contraction over anchors (0 x NaN)
+    const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+    xb[0] = active ? (f32x4){f0.x, f0.y, f0.z, f0.w} : zero;
+    xb[1] = active ? (f32x4){f1.x, f1.y, f1.z, f1.w} : zero;
+    xb[2] = !active ? zero : (kk == 0 ? (f32x4){vw[0], vw[1], vw[2], dist} : (kk == 1 ? (f32x4){lv, 1.0f, 0.0f, 0.0f} : zero));
 }
 
 // pre1^T tiles of one head: acc[ht][r] = pre-activation of hidden unit 16 ht + 4 kk + r.  w1: LDS slots [ht 2][t 3][r 4] of that head
@@ -1031,7 +1033,8 @@ extern "C" int gsd_backward(const gsd_cfg* cfg, const gsd_inputs* in, const gsd_
     }
     if (!scratch || scratch_bytes < gsd_backward_scratch_bytes(cfg)) { gsr_set_error("gsd_backward: scratch too small"); return 1; }
     const int k = cfg->k;
-    if (cfg->Nv == 0) {       // no anchors: all parameter gradients are zero
+    if (cfg->Nv == 0 || P == 0) {       // no anchors, or every gate closed (no output row, the out-gradient tensors are empty): all parameter gradients are zero;
+                                        // the per-anchor gradients are the caller's zero-filled buffers
         const int lv = cfg->level ? 1 : 0;
         (void)gsr_memset_async(g.W1o, 0, sizeof(float) * 32 * (35 + (cfg->dist_o ? 1 : 0) + lv), s); (void)gsr_memset_async(g.b1o, 0, sizeof(float) * 32, s);
         (void)gsr_memset_async(g.W1c, 0, sizeof(float) * 32 * (35 + (cfg->dist_c ? 1 : 0) + lv), s); (void)gsr_memset_async(g.b1c, 0, sizeof(float) * 32, s);
@@ -1045,7 +1048,6 @@ extern "C" int gsd_backward(const gsd_cfg* cfg, const gsd_inputs* in, const gsd_
     if (!og || !og->xyz || !og->color || !og->opacity || !og->scaling || !og->rot || !ig->anchor || !ig->feat || !ig->offset || !ig->scaling ||
         !neural_opacity || !row_offset) { gsr_set_error("gsd_backward: null gradient pointer"); return 1; }
     if (((uintptr_t)og->rot | (uintptr_t)ig->feat) & 15) { gsr_set_error("gsd_backward: dL_drot / d_feat must be 16-byte aligned"); return 1; }
-    (void)P;
     const size_t ld = bwd_ld(cfg);
     const float* img = fwd_scratch ? (const float*)fwd_scratch : (const float*)scratch;
     float* sc = (float*)((char*)scratch + gsr_align(IMG_FLOATS * sizeof(float)));
