@@ -1,0 +1,402 @@
+// gsr_anchor.hip -- Scaffold-GS / Octree-GS densification geometry on the device (include/gsrast.h gsr_anchor_*, gsr_rows_*).
+//
+// One growing level (ScaffoldGaussian.anchor_growing, gssr/gaussian/scaffold_gaussian.py:555-649; the loop body of OctreeGaussian.anchor_growing,
+// octree_gaussian.py:401-534): the reference compares every unique candidate cell against every anchor (O(U N), chunks of 4096), after a
+// torch.unique(dim=0) and before a scatter_max.  Here the cells of the admitted anchors and of the candidate slots are packed into 64-bit keys
+// (21 bits per axis + a tag bit that puts an occupied entry in front of the candidates of its cell) and sorted together by gsr_radix_sort_pairs
+// (low word, then stable by the high word); a run of equal cells that STARTS with a candidate is a new anchor.  Run heads come out in key
+// order = lexicographic signed (x, y, z), the order of torch.unique(dim=0).  Everything is integer compares and maxima: bitwise deterministic.
+//
+// This unit is built with -ffp-contract=off: the cell of a point is an integer output and must not depend on FMA contraction.
+#include "gsr_common.h"
+
+#define ANC_BLOCK 1024
+#define ANC_BIAS 1048576            // 2^20: cells in [-2^20, 2^20 - 1] per axis
+#define ANC_CNT_ENTRIES 0           // counters: entries in the sort
+#define ANC_CNT_HEADS 1             //           new anchors
+
+__device__ __forceinline__ uint32_t anc_wave_incl_scan(uint32_t v)
+{
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(v, d, 64);
+        if ((int)lane >= d) v += t;
+    }
+    return v;
+}
+// block-wide exclusive scan over blockDim.x <= 1024 threads; *total = block sum.  lds: 17 words
+__device__ __forceinline__ uint32_t anc_block_excl_scan(uint32_t v, uint32_t* lds, uint32_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const uint32_t s = anc_wave_incl_scan(v);
+    if (lane == 63) lds[wave] = s;
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t w = (lane < nw) ? lds[lane] : 0;
+        const uint32_t ws = anc_wave_incl_scan(w);
+        if (lane < nw) lds[lane] = ws - w;
+        if (lane == nw - 1) lds[16] = ws;
+    }
+    __syncthreads();
+    const uint32_t r = s - v + lds[wave];
+    *total = lds[16];
+    __syncthreads();
+    return r;
+}
+
+// in-place exclusive scan of the n block sums by ONE block; the total goes to *total_out
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_scan_sums(uint32_t* __restrict__ sums, uint32_t n, uint32_t* __restrict__ total_out)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t chunk = (n + ANC_BLOCK - 1) / ANC_BLOCK;
+    const uint32_t b = min(n, threadIdx.x * chunk), e = min(n, b + chunk);
+    uint32_t sum = 0;
+    for (uint32_t i = b; i < e; i++) sum += sums[i];
+    uint32_t tot;
+    uint32_t run = anc_block_excl_scan(sum, lds, &tot);
+    for (uint32_t i = b; i < e; i++) { const uint32_t v = sums[i]; sums[i] = run; run += v; }
+    if (threadIdx.x == 0) *total_out = tot;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- entries of a level
+// c = rint((p - origin) / cell): round-half-even, IEEE division (no reciprocal), every operation rounded on its own
+__device__ __forceinline__ bool anc_cell_key(float px, float py, float pz, const gsr_anchor_level& L, uint64_t* key63)
+{
+    const float rx = rintf(__fdiv_rn(px - L.origin[0], L.cell)), ry = rintf(__fdiv_rn(py - L.origin[1], L.cell)),
+                rz = rintf(__fdiv_rn(pz - L.origin[2], L.cell));
+    const float lo = -(float)ANC_BIAS, hi = (float)(ANC_BIAS - 1);
+    if (!(rx >= lo && rx <= hi && ry >= lo && ry <= hi && rz >= lo && rz <= hi)) return false;       // NaN and infinities fail too
+    const uint64_t ux = (uint64_t)((int)rx + ANC_BIAS), uy = (uint64_t)((int)ry + ANC_BIAS), uz = (uint64_t)((int)rz + ANC_BIAS);
+    *key63 = (ux << 42) | (uy << 21) | uz;
+    return true;
+}
+
+// Entry i of the level: i < Na the cell of anchor i (tag 0), otherwise candidate slot i - Na (tag 1).  Returns whether the entry takes part.
+__device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L, uint64_t* key, uint32_t* status)
+{
+    const uint32_t Na = (uint32_t)L.Na, N0 = (uint32_t)L.N0;
+    uint64_t k63;
+    if (i < Na) {
+        if (i < N0 && L.mask && !L.mask[i]) return false;
+        // an anchor outside the packing range cannot share a cell with a candidate inside it: it is left out, not an error
+        if (!anc_cell_key(L.anchor[3 * (size_t)i], L.anchor[3 * (size_t)i + 1], L.anchor[3 * (size_t)i + 2], L, &k63)) return false;
+        *key = k63 << 1;
+        return true;
+    }
+    const uint32_t j = i - Na, a = j / (uint32_t)L.k;
+    const float g = L.grads[j];
+    if (!(g >= L.thr_lo && g < L.thr_hi) || !L.offset_mask[j]) return false;
+    if (L.rand && !(L.rand[j] > L.rand_thr)) return false;
+    if (L.mask && !L.mask[a]) return false;
+    const float* sc = L.scaling + (size_t)a * L.scaling_stride;
+    const float mx = L.offset[3 * (size_t)j] * sc[0], my = L.offset[3 * (size_t)j + 1] * sc[1], mz = L.offset[3 * (size_t)j + 2] * sc[2];
+    const float px = L.anchor[3 * (size_t)a] + mx, py = L.anchor[3 * (size_t)a + 1] + my, pz = L.anchor[3 * (size_t)a + 2] + mz;
+    if (!anc_cell_key(px, py, pz, L, &k63)) { atomicOr(status + 1, 1u); return false; }      // sticky: the cell does not fit 21 bits per axis
+    *key = (k63 << 1) | 1u;
+    return true;
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_count(gsr_anchor_level L, uint32_t cap, uint32_t* __restrict__ sums, uint32_t* __restrict__ status)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    uint64_t key;
+    const uint32_t f = (i < cap && anc_entry(i, L, &key, status)) ? 1u : 0u;
+    uint32_t tot;
+    anc_block_excl_scan(f, lds, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_place(gsr_anchor_level L, uint32_t cap, const uint32_t* __restrict__ sums, uint32_t* __restrict__ status,
+                                                               uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi, uint32_t* __restrict__ sort_keys,
+                                                               uint32_t* __restrict__ src)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    uint64_t key = 0;
+    const bool f = i < cap && anc_entry(i, L, &key, status);
+    uint32_t tot;
+    const uint32_t pos = sums[blockIdx.x] + anc_block_excl_scan(f ? 1u : 0u, lds, &tot);       // < cap: at most one position per entry
+    if (f) { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
+}
+
+__global__ void __launch_bounds__(256) k_anc_gather_hi(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_hi,
+                                                       uint32_t* __restrict__ keys)
+{
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p < *n_dev) keys[p] = key_hi[perm[p]];
+}
+
+// sorted position p starts a new anchor iff it holds a candidate and the entry before it lies in another cell (occupied entries lead their run)
+__device__ __forceinline__ bool anc_is_head(uint32_t p, uint32_t n, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_lo)
+{
+    if (p >= n) return false;
+    const uint64_t k = ((uint64_t)hi[p] << 32) | key_lo[perm[p]];
+    if (!(k & 1u)) return false;
+    if (p == 0) return true;
+    const uint64_t q = ((uint64_t)hi[p - 1] << 32) | key_lo[perm[p - 1]];
+    return (q >> 1) != (k >> 1);
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_count(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm,
+                                                              const uint32_t* __restrict__ key_lo, uint32_t* __restrict__ sums)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t f = anc_is_head(blockIdx.x * ANC_BLOCK + threadIdx.x, *n_dev, hi, perm, key_lo) ? 1u : 0u;
+    uint32_t tot;
+    anc_block_excl_scan(f, lds, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_place(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm,
+                                                              const uint32_t* __restrict__ key_lo, const uint32_t* __restrict__ sums, uint32_t* __restrict__ head_pos)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t p = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    const bool f = anc_is_head(p, *n_dev, hi, perm, key_lo);
+    uint32_t tot;
+    const uint32_t q = sums[blockIdx.x] + anc_block_excl_scan(f ? 1u : 0u, lds, &tot);        // q <= p < capacity
+    if (f) head_pos[q] = p;
+}
+
+__global__ void __launch_bounds__(64) k_anc_publish(const uint32_t* __restrict__ counters, uint32_t* __restrict__ status)
+{
+    if (threadIdx.x == 0) status[0] = counters[ANC_CNT_HEADS];
+}
+
+// new_anchor = float(c) * cell + origin (a multiply, then an add); new_feat = element-wise maximum of anchor_feat over the run's candidates
+__global__ void __launch_bounds__(256) k_anc_emit(gsr_anchor_level L, uint32_t count, const uint32_t* __restrict__ counters, const uint32_t* __restrict__ hi,
+                                                  const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_lo, const uint32_t* __restrict__ src,
+                                                  const uint32_t* __restrict__ head_pos, float* __restrict__ new_anchor, float* __restrict__ new_feat)
+{
+    const uint32_t F = (uint32_t)L.F, per = F > 0 ? F : 1u;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t q = (uint32_t)(t / per), f = (uint32_t)(t % per);
+    if (q >= count || q >= counters[ANC_CNT_HEADS]) return;
+    const uint32_t n = counters[ANC_CNT_ENTRIES];
+    uint32_t p = head_pos[q];
+    const uint64_t cellkey = (((uint64_t)hi[p] << 32) | key_lo[perm[p]]) >> 1;
+    if (f == 0) {
+        const int cx = (int)((cellkey >> 42) & 0x1FFFFFu) - ANC_BIAS, cy = (int)((cellkey >> 21) & 0x1FFFFFu) - ANC_BIAS, cz = (int)(cellkey & 0x1FFFFFu) - ANC_BIAS;
+        const float ax = (float)cx * L.cell, ay = (float)cy * L.cell, az = (float)cz * L.cell;
+        new_anchor[3 * (size_t)q] = ax + L.origin[0]; new_anchor[3 * (size_t)q + 1] = ay + L.origin[1]; new_anchor[3 * (size_t)q + 2] = az + L.origin[2];
+    }
+    if (F == 0) return;
+    float m = 0.f;
+    bool first = true;
+    for (; p < n; p++) {                                         // every entry of the run is a candidate: an occupied entry would have led it
+        const uint32_t e = perm[p];
+        if (!first && ((((uint64_t)hi[p] << 32) | key_lo[e]) >> 1) != cellkey) break;
+        const uint32_t a = (src[e] - (uint32_t)L.Na) / (uint32_t)L.k;
+        const float v = L.anchor_feat[(size_t)a * F + f];
+        m = (first || v > m) ? v : m;
+        first = false;
+    }
+    new_feat[(size_t)q * F + f] = m;
+}
+
+struct AncScratch { uint32_t *sums, *key_lo, *key_hi, *src, *ka, *kb, *va, *vb, *hist, *counters; size_t bytes; };
+static AncScratch anc_carve(uint32_t cap, void* base)
+{
+    AncScratch a; char* p = (char*)base;
+    const size_t n = cap > 0 ? cap : 1;
+    auto take = [&](size_t bytes) { char* r = p; p += gsr_align(bytes); return (uint32_t*)r; };
+    a.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4);
+    a.key_lo = take(n * 4); a.key_hi = take(n * 4); a.src = take(n * 4);
+    a.ka = take(n * 4); a.kb = take(n * 4); a.va = take(n * 4); a.vb = take(n * 4);
+    a.hist = take(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256) * 4);
+    a.counters = take(64);
+    a.bytes = (size_t)(p - (char*)base);
+    return a;
+}
+
+static int anc_check(const gsr_anchor_level* lv, const char* who, uint32_t* cap)
+{
+    if (!lv) { gsr_set_error("%s: level is NULL", who); return 1; }
+    if (lv->N0 < 0 || lv->Na < lv->N0) { gsr_set_error("%s: bad sizes Na=%d N0=%d", who, lv->Na, lv->N0); return 1; }
+    if (lv->k < 1) { gsr_set_error("%s: n_offsets k=%d must be >= 1", who, lv->k); return 1; }
+    if (lv->F < 0) { gsr_set_error("%s: feat_dim F=%d must be >= 0", who, lv->F); return 1; }
+    if (lv->scaling_stride < 3) { gsr_set_error("%s: scaling_stride=%d must be >= 3", who, lv->scaling_stride); return 1; }
+    if (!(lv->cell > 0.0f) || !(lv->cell < 3.0e38f)) { gsr_set_error("%s: cell must be a positive finite number", who); return 1; }
+    const uint64_t c = (uint64_t)lv->Na + (uint64_t)lv->N0 * (uint64_t)lv->k;
+    if (c >= (1ull << 31)) { gsr_set_error("%s: Na + N0 * k = %llu entries exceed 2^31", who, (unsigned long long)c); return 1; }
+    if (lv->Na && !lv->anchor) { gsr_set_error("%s: anchor is NULL", who); return 1; }
+    if (lv->N0 && (!lv->offset || !lv->scaling || !lv->grads || !lv->offset_mask || (lv->F && !lv->anchor_feat))) {
+        gsr_set_error("%s: offset / scaling / anchor_feat / grads / offset_mask must be provided", who); return 1;
+    }
+    *cap = (uint32_t)c;
+    return 0;
+}
+
+extern "C" size_t gsr_anchor_level_scratch_bytes(int32_t Na, int32_t N0, int32_t k)
+{
+    if (Na < 0 || N0 < 0 || k < 1) return 0;
+    const uint64_t c = (uint64_t)Na + (uint64_t)N0 * (uint64_t)k;
+    if (c >= (1ull << 31)) return 0;
+    return anc_carve((uint32_t)c, nullptr).bytes;
+}
+
+extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, size_t scratch_bytes, uint32_t* status_dev, void* stream)
+{
+    uint32_t cap;
+    if (anc_check(lv, "anchor_level_find", &cap)) return 1;
+    if (!status_dev) { gsr_set_error("anchor_level_find: status_dev is NULL"); return 1; }
+    const AncScratch a = anc_carve(cap, scratch);
+    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("anchor_level_find: scratch too small: %zu < %zu", scratch_bytes, a.bytes); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (gsr_memset_async(a.counters, 0, 64, s)) { gsr_set_error("anchor_level_find: counters"); return 1; }
+    if (cap) {
+        const uint32_t nblk = gsr_div_up(cap, ANC_BLOCK);
+        hipLaunchKernelGGL(k_anc_entry_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev);
+        hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, a.sums, nblk, a.counters + ANC_CNT_ENTRIES);
+        hipLaunchKernelGGL(k_anc_entry_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev, a.key_lo, a.key_hi, a.ka, a.src);
+        const uint32_t* n_dev = a.counters + ANC_CNT_ENTRIES;
+        uint32_t *k0 = a.ka, *v0 = a.va, *k1 = a.kb, *v1 = a.vb;
+        bool in_b = false;
+        if (gsr_radix_sort_pairs(k0, v0, k1, v1, cap, n_dev, 0, 32, 8, true, a.hist, &in_b, s)) return 1;
+        if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
+        hipLaunchKernelGGL(k_anc_gather_hi, dim3(gsr_div_up(cap, 256)), dim3(256), 0, s, n_dev, v0, a.key_hi, k0);
+        if (gsr_radix_sort_pairs(k0, v0, k1, v1, cap, n_dev, 0, 32, 8, false, a.hist, &in_b, s)) return 1;
+        if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
+        // both sorts run 4 passes of 8 bits: the order ends in (ka, va), the run heads go to kb -- gsr_anchor_level_emit relies on it
+        if (k0 != a.ka || v0 != a.va) { gsr_set_error("anchor_level_find: unexpected sort buffer parity"); return 1; }
+        hipLaunchKernelGGL(k_anc_head_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums);
+        hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, a.sums, nblk, a.counters + ANC_CNT_HEADS);
+        hipLaunchKernelGGL(k_anc_head_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums, a.kb);
+    }
+    hipLaunchKernelGGL(k_anc_publish, dim3(1), dim3(64), 0, s, a.counters, status_dev);
+    return gsr_check_launch("anchor_level_find", s, false);
+}
+
+extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scratch, size_t scratch_bytes, uint32_t count, float* new_anchor, float* new_feat,
+                                     void* stream)
+{
+    uint32_t cap;
+    if (anc_check(lv, "anchor_level_emit", &cap)) return 1;
+    const AncScratch a = anc_carve(cap, const_cast<void*>(scratch));
+    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("anchor_level_emit: scratch too small: %zu < %zu", scratch_bytes, a.bytes); return 1; }
+    if (count == 0) return 0;
+    if (count > (uint32_t)lv->N0 * (uint32_t)lv->k) { gsr_set_error("anchor_level_emit: count %u exceeds the N0 * k candidate slots", count); return 1; }
+    if (!new_anchor || (lv->F && !new_feat)) { gsr_set_error("anchor_level_emit: new_anchor / new_feat is NULL"); return 1; }
+    const size_t threads = (size_t)count * (size_t)(lv->F > 0 ? lv->F : 1);
+    if ((threads + 255) / 256 >= (1ull << 31)) { gsr_set_error("anchor_level_emit: count * F too large"); return 1; }
+    hipLaunchKernelGGL(k_anc_emit, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lv, count, a.counters, a.ka, a.va, a.key_lo, a.src,
+                       a.kb, new_anchor, new_feat);
+    return gsr_check_launch("anchor_level_emit", (hipStream_t)stream, false);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rows: compact + append
+// dst = [src[keep] ; tail] for many tensors that share one keep mask over N rows (the reference's per-tensor x[mask] + cat over six parameters,
+// twelve Adam moments and four accumulators: ~60 launches and a nonzero() synchronisation each).  The keep -> position scan runs once.
+#define GSR_ROWS_MAX 24
+#define GSR_ROWS_CHUNK 2048          // copy units per block
+struct RowsEntry { const char* src; char* dst; const char* tail; uint64_t units_keep, units_all; uint32_t upr, ulog, first_block, pad_; };   // upr: units per row
+struct RowsTable { int32_t count; RowsEntry e[GSR_ROWS_MAX]; };
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_rows_count(const uint8_t* __restrict__ keep, uint32_t N, uint32_t* __restrict__ sums)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    uint32_t tot;
+    anc_block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(ANC_BLOCK) k_rows_pos(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ pos)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    uint32_t tot;
+    const uint32_t p = sums[blockIdx.x] + anc_block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
+    if (i < N) pos[i] = p;
+}
+
+template <typename T>
+__device__ __forceinline__ void rows_copy(const RowsEntry& E, uint64_t base, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ pos, uint32_t n_keep)
+{
+    const T* src = reinterpret_cast<const T*>(E.src);
+    const T* tail = reinterpret_cast<const T*>(E.tail);
+    T* dst = reinterpret_cast<T*>(E.dst);
+    const uint64_t end = min(E.units_all, base + GSR_ROWS_CHUNK);
+    T zero;
+    memset(&zero, 0, sizeof(T));
+    for (uint64_t u = base + threadIdx.x; u < end; u += 256) {
+        if (u < E.units_keep) {
+            const uint32_t r = (uint32_t)(u / E.upr), c = (uint32_t)(u - (uint64_t)r * E.upr);
+            if (keep[r]) dst[(uint64_t)pos[r] * E.upr + c] = src[u];
+        } else {
+            const uint64_t v = u - E.units_keep;
+            dst[(uint64_t)n_keep * E.upr + v] = tail ? tail[v] : zero;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_rows_compact(RowsTable T, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ n_keep_dev)
+{
+    int k = 0;
+#pragma unroll 1
+    for (int i = 1; i < T.count; i++) k = (blockIdx.x >= T.e[i].first_block) ? i : k;
+    const RowsEntry& E = T.e[k];
+    const uint64_t base = (uint64_t)(blockIdx.x - E.first_block) * GSR_ROWS_CHUNK;
+    const uint32_t n_keep = *n_keep_dev;
+    if (E.ulog == 4) rows_copy<uint4>(E, base, keep, pos, n_keep);
+    else if (E.ulog == 3) rows_copy<uint2>(E, base, keep, pos, n_keep);
+    else rows_copy<uint32_t>(E, base, keep, pos, n_keep);
+}
+
+struct RowsScratch { uint32_t *sums, *pos, *count; size_t bytes; };
+static RowsScratch rows_carve(uint32_t N, void* base)
+{
+    RowsScratch r; char* p = (char*)base;
+    const size_t n = N > 0 ? N : 1;
+    auto take = [&](size_t bytes) { char* q = p; p += gsr_align(bytes); return (uint32_t*)q; };
+    r.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4); r.pos = take(n * 4); r.count = take(64);
+    r.bytes = (size_t)(p - (char*)base);
+    return r;
+}
+extern "C" size_t gsr_rows_compact_scratch_bytes(int64_t N)
+{
+    if (N < 0 || N >= (1ll << 31)) return 0;
+    return rows_carve((uint32_t)N, nullptr).bytes;
+}
+
+extern "C" int gsr_rows_compact_multi(int64_t N, const uint8_t* keep, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
+                                      void* stream)
+{
+    if (N < 0 || N >= (1ll << 31)) { gsr_set_error("rows_compact_multi: N=%lld out of range", (long long)N); return 1; }
+    if (N > 0 && !keep) { gsr_set_error("rows_compact_multi: keep is NULL"); return 1; }
+    if (count < 0 || (count > 0 && !t)) { gsr_set_error("rows_compact_multi: bad table"); return 1; }
+    const RowsScratch r = rows_carve((uint32_t)N, scratch);
+    if (!scratch || r.bytes > scratch_bytes) { gsr_set_error("rows_compact_multi: scratch too small: %zu < %zu", scratch_bytes, r.bytes); return 1; }
+    for (int32_t i = 0; i < count; i++) {
+        const gsr_rows_tensor& a = t[i];
+        if (a.row_bytes <= 0 || (a.row_bytes & 3) || a.n_tail < 0) { gsr_set_error("rows_compact_multi: tensor %d: row_bytes must be a positive multiple of 4, n_tail >= 0", i); return 1; }
+        if (!a.dst || (N > 0 && !a.src)) { gsr_set_error("rows_compact_multi: tensor %d: null pointer", i); return 1; }
+        if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.tail) & 3) { gsr_set_error("rows_compact_multi: tensor %d: pointers must be 4-byte aligned", i); return 1; }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t nblk = gsr_div_up((uint32_t)(N > 0 ? N : 1), ANC_BLOCK);
+    hipLaunchKernelGGL(k_rows_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums);
+    hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, r.sums, nblk, r.count);
+    hipLaunchKernelGGL(k_rows_pos, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums, r.pos);
+    int32_t i = 0;
+    while (i < count) {
+        RowsTable T; T.count = 0;
+        uint64_t blocks = 0;
+        for (; i < count && T.count < GSR_ROWS_MAX; i++) {
+            const gsr_rows_tensor& a = t[i];
+            const uintptr_t al = (uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.tail | (uintptr_t)a.row_bytes;
+            const uint32_t ulog = (al & 15) == 0 ? 4u : ((al & 7) == 0 ? 3u : 2u);
+            RowsEntry& E = T.e[T.count];
+            E.src = (const char*)a.src; E.dst = (char*)a.dst; E.tail = (const char*)a.tail; E.ulog = ulog; E.upr = (uint32_t)(a.row_bytes >> ulog); E.pad_ = 0;
+            E.units_keep = (uint64_t)N * E.upr; E.units_all = E.units_keep + (uint64_t)a.n_tail * E.upr;
+            if (E.units_all == 0) continue;
+            E.first_block = (uint32_t)blocks;
+            blocks += (E.units_all + GSR_ROWS_CHUNK - 1) / GSR_ROWS_CHUNK;
+            if (blocks >= (1ull << 31)) { gsr_set_error("rows_compact_multi: tensor %d: too many bytes for one launch", i); return 1; }
+            T.count++;
+        }
+        if (blocks) hipLaunchKernelGGL(k_rows_compact, dim3((uint32_t)blocks), dim3(256), 0, s, T, keep, r.pos, r.count);
+    }
+    return gsr_check_launch("rows_compact_multi", s, false);
+}

@@ -1,0 +1,338 @@
+"""Anchor growing and pruning of the Scaffold-GS models on the device (include/gsrast.h gsr_anchor_level_*, gsr_rows_compact_multi).
+
+`adjust_anchor_(model)` replaces `ScaffoldGaussian.adjust_anchor` (gssr/gaussian/scaffold_gaussian.py:651-705) and the `anchor_growing` it calls
+(:555-649): the consumer of the statistics `gsrast.decode.training_stats_` accumulates.  The reference compares every unique candidate cell with
+every anchor (O(U N)), runs a `torch.unique(dim=0)` and a `torch_scatter.scatter_max` per level and then ~60 boolean-index / cat operations, each
+with a `nonzero()` host synchronisation; here a level is one sort over packed cell keys and the prune + append of every parameter, Adam moment and
+accumulator is one launch.  Results equal the reference's bit for bit (tests/test_gpu_anchor.py against fixtures its own code produced), with the
+two deviations of DESIGN.md §7: cells must fit 21 bits per axis, and the division by the cell size is a true division.
+
+There is no CPU fallback: host tensors raise."""
+import ctypes as C
+import math
+
+import torch
+
+from . import check, lib, ptr, stream_ptr
+
+_vp = C.c_void_p
+PARAM_ATTRS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
+_SKIP = ("mlp", "conv", "feat_base", "embedding")        # param groups the reference's optimizer surgery leaves alone
+
+
+class Level(C.Structure):                 # include/gsrast.h gsr_anchor_level
+    _fields_ = [("Na", C.c_int32), ("N0", C.c_int32), ("k", C.c_int32), ("F", C.c_int32), ("scaling_stride", C.c_int32),
+                ("thr_lo", C.c_float), ("thr_hi", C.c_float), ("rand_thr", C.c_float), ("cell", C.c_float), ("origin", C.c_float * 3),
+                ("anchor", _vp), ("mask", _vp), ("offset", _vp), ("scaling", _vp), ("anchor_feat", _vp), ("grads", _vp), ("offset_mask", _vp), ("rand", _vp)]
+
+
+class RowsTensor(C.Structure):            # include/gsrast.h gsr_rows_tensor
+    _fields_ = [("src", _vp), ("dst", _vp), ("tail", _vp), ("row_bytes", C.c_int64), ("n_tail", C.c_int64)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = lib()
+    if not _bound:
+        sz = C.c_size_t
+        L.gsr_anchor_level_scratch_bytes.restype = sz; L.gsr_anchor_level_scratch_bytes.argtypes = [C.c_int32] * 3
+        L.gsr_anchor_level_find.restype = C.c_int
+        L.gsr_anchor_level_find.argtypes = [C.POINTER(Level), _vp, sz, _vp, _vp]
+        L.gsr_anchor_level_emit.restype = C.c_int
+        L.gsr_anchor_level_emit.argtypes = [C.POINTER(Level), _vp, sz, C.c_uint32, _vp, _vp, _vp]
+        L.gsr_rows_compact_scratch_bytes.restype = sz; L.gsr_rows_compact_scratch_bytes.argtypes = [C.c_int64]
+        L.gsr_rows_compact_multi.restype = C.c_int
+        L.gsr_rows_compact_multi.argtypes = [C.c_int64, _vp, C.c_int32, C.POINTER(RowsTensor), _vp, sz, _vp]
+        _bound = True
+    return L
+
+
+def _f32(t, name, shape=None):
+    """A contiguous float32 HIP tensor, or a RuntimeError that names the argument."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name} must be a tensor")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: expected scalar type Float but found {t.dtype}")
+    if shape is not None and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise RuntimeError(f"{name}: expected shape {list(shape)} but found {list(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    return t.detach().contiguous()
+
+
+def _bytes(t, name, n, like):
+    """bool / uint8 mask of n entries on the device of `like`, as bytes."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name} must be a tensor")
+    if not t.is_cuda or t.device != like.device:
+        raise RuntimeError(f"{name} must be a CUDA tensor on the device of the other arguments")
+    if t.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"{name}: expected a bool or uint8 mask but found {t.dtype}")
+    if t.numel() != n:
+        raise RuntimeError(f"{name}: expected {n} entries but found {t.numel()}")
+    t = t.detach().contiguous().reshape(-1)
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell, thr_lo, thr_hi=math.inf, rand=None, rand_thr=0.0, mask=None,
+               origin=(0.0, 0.0, 0.0), n0=None):
+    """One growing level (gsr_anchor_level_find + gsr_anchor_level_emit) -> (new_anchor [U,3], new_feat [U,F]).
+
+    anchor [Na,3]: the first n0 (default: all) own the candidate slots offset [n0,k,3] / grads [n0*k] / offset_mask [n0*k]; the others only occupy
+    cells.  scaling [n0,>=3] is the ACTIVATED scaling, anchor_feat [n0,F].  Slot j is a candidate iff thr_lo <= grads[j] < thr_hi, offset_mask[j],
+    rand[j] > rand_thr (rand given) and mask[j // k] (mask [n0] given; a masked-out original anchor does not occupy its cell either).  The new
+    anchors are the distinct cells rint((anchor + offset * scaling - origin) / cell) of the candidates that hold no admitted anchor, in (x, y, z)
+    order, at cell * c + origin, with the element-wise maximum of the candidates' features.  One host synchronisation (the count)."""
+    anchor = _f32(anchor, "anchor", (None, 3))
+    Na = anchor.shape[0]
+    N0 = Na if n0 is None else int(n0)
+    if not 0 <= N0 <= Na:
+        raise RuntimeError(f"n0: expected 0 <= n0 <= {Na} but found {N0}")
+    offset = _f32(offset, "offset", (N0, None, 3))
+    k = offset.shape[1]
+    if k < 1:
+        raise RuntimeError("offset: n_offsets must be >= 1")
+    scaling = _f32(scaling, "scaling", (N0, None))
+    if scaling.shape[1] < 3:
+        raise RuntimeError(f"scaling: expected at least 3 columns but found {scaling.shape[1]}")
+    anchor_feat = _f32(anchor_feat, "anchor_feat", (N0, None))
+    F = anchor_feat.shape[1]
+    grads = _f32(grads, "grads")
+    if grads.numel() != N0 * k:
+        raise RuntimeError(f"grads: expected {N0 * k} entries but found {grads.numel()}")
+    offset_mask = _bytes(offset_mask, "offset_mask", N0 * k, anchor)
+    if rand is not None:
+        rand = _f32(rand, "rand")
+        if rand.numel() != N0 * k:
+            raise RuntimeError(f"rand: expected {N0 * k} entries but found {rand.numel()}")
+    if mask is not None:
+        mask = _bytes(mask, "mask", N0, anchor)
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise RuntimeError(f"cell: expected a positive finite number but found {cell}")
+    if len(origin) != 3:
+        raise RuntimeError("origin: expected three numbers")
+    for name, t in (("offset", offset), ("scaling", scaling), ("anchor_feat", anchor_feat), ("grads", grads), ("rand", rand)):
+        if t is not None and t.device != anchor.device:
+            raise RuntimeError(f"{name} must be on the device of anchor")
+    if Na + N0 * k >= 1 << 31:
+        raise RuntimeError(f"anchor: Na + n0 * k = {Na + N0 * k} entries exceed 2^31")
+    L = _lib()
+    dev = anchor.device
+    lv = Level(Na, N0, k, F, scaling.shape[1], thr_lo, thr_hi, rand_thr, cell, (C.c_float * 3)(*[float(o) for o in origin]),
+               ptr(anchor).value, None if mask is None else ptr(mask).value, ptr(offset).value, ptr(scaling).value, ptr(anchor_feat).value, ptr(grads).value,
+               ptr(offset_mask).value, None if rand is None else ptr(rand).value)
+    with torch.cuda.device(dev):
+        nbytes = L.gsr_anchor_level_scratch_bytes(Na, N0, k)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        check(L.gsr_anchor_level_find(C.byref(lv), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)), "anchor_level_find")
+        count, overflow = status.tolist()                     # the level's one host synchronisation
+        if overflow:
+            raise RuntimeError(f"gsrast anchor growing: a candidate cell lies outside the packing range of +-2^20 cells per axis "
+                               f"(cell size {cell:g}: about +-{cell * (1 << 20):g} scene units around the origin)")
+        new_anchor = torch.empty(count, 3, dtype=torch.float32, device=dev)
+        new_feat = torch.empty(count, F, dtype=torch.float32, device=dev)
+        if count:
+            check(L.gsr_anchor_level_emit(C.byref(lv), ptr(scratch), nbytes, count, ptr(new_anchor), ptr(new_feat), stream_ptr(dev)), "anchor_level_emit")
+    return new_anchor, new_feat
+
+
+def _host_log(x):
+    """log of a float32 scalar as torch's CPU kernel computes it for a float32 tensor (the vector path: 16 lanes)."""
+    return float(torch.log(torch.full((16,), x, dtype=torch.float32))[0])
+
+
+def anchor_growing(anchor, offset, scaling, anchor_feat, grads, offset_mask, threshold, *, voxel_size, n_offsets, update_depth=3, update_init_factor=16,
+                   update_hierachy_factor=4, rand=None, generator=None):
+    """The reference's anchor_growing: every level's new anchors, concatenated in level order, as its dictionary `d`
+    (anchor, scaling, rotation, anchor_feat, offset, opacity) -- handing the whole to cat_tensors_to_optimizer once equals the reference's call per level.
+    `scaling` is the ACTIVATED get_scaling tensor as torch computed it; `rand`: one tensor of uniform draws [N*k] per level (None: drawn on the
+    device from `generator`)."""
+    anchor = _f32(anchor, "anchor", (None, 3))
+    N0 = anchor.shape[0]
+    k = int(n_offsets)
+    offset = _f32(offset, "offset", (N0, k, 3))
+    if update_depth < 0 or update_init_factor < 1 or update_hierachy_factor < 1:
+        raise RuntimeError("update_depth / update_init_factor / update_hierachy_factor: expected update_depth >= 0 and factors >= 1")
+    if not (float(voxel_size) > 0.0):
+        raise RuntimeError(f"voxel_size: expected a positive number but found {voxel_size}")
+    if rand is not None and len(rand) != update_depth:
+        raise RuntimeError(f"rand: expected a list of update_depth = {update_depth} tensors but found {len(rand)}")
+    dev = anchor.device
+    added, feats, sizes = [], [], []
+    for i in range(update_depth):
+        cur_threshold = threshold * ((update_hierachy_factor // 2) ** i)
+        r = rand[i] if rand is not None else torch.rand(N0 * k, dtype=torch.float32, device=dev, generator=generator)      # drawn at every level, as the reference does
+        if i > 0 and not added:
+            continue                                             # scaffold_gaussian.py:569-572: later levels wait for a first addition
+        size_factor = update_init_factor // (update_hierachy_factor ** i)
+        if size_factor < 1:
+            raise RuntimeError(f"update_depth: level {i} has size factor {update_init_factor} // {update_hierachy_factor}**{i} = 0")
+        cur_size = voxel_size * size_factor
+        cur = torch.cat([anchor] + added) if added else anchor
+        a, f = grow_level(cur, offset, scaling, anchor_feat, grads, offset_mask, cell=cur_size, thr_lo=cur_threshold, rand=r, rand_thr=0.5 ** (i + 1), n0=N0)
+        if a.shape[0]:
+            added.append(a); feats.append(f); sizes.append((a.shape[0], cur_size))
+    U = sum(n for n, _ in sizes)
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    new_scaling = z(U, 6)
+    p = 0
+    for n, cur_size in sizes:
+        new_scaling[p:p + n] = _host_log(C.c_float(cur_size).value)
+        p += n
+    new_rotation = z(U, 4)
+    new_rotation[:, 0] = 1.0
+    x = C.c_float(0.1).value                                     # inverse_sigmoid(0.1 * ones) in float32
+    xt = torch.full((16,), x, dtype=torch.float32)
+    new_opacity = torch.full((U, 1), float(torch.log(xt / (1 - xt))[0]), dtype=torch.float32, device=dev)
+    return {"anchor": torch.cat(added) if added else z(0, 3), "scaling": new_scaling, "rotation": new_rotation,
+            "anchor_feat": torch.cat(feats) if feats else z(0, anchor_feat.shape[1]), "offset": z(U, k, 3), "opacity": new_opacity}
+
+
+def rows_compact(keep, tensors, tails=None):
+    """[torch.cat((x[keep], tail)) for x, tail in zip(tensors, tails)] in one launch (gsr_rows_compact_multi): `keep` a bool / uint8 mask over the
+    rows (dim 0) of every tensor; a tail is a tensor with the same row shape, or an int = that many rows of zeros (None: 0).  One host
+    synchronisation: the number of kept rows sizes the results."""
+    if not tensors:
+        return []
+    N = tensors[0].shape[0]
+    keep = _bytes(keep, "keep", N, tensors[0])
+    tails = list(tails) if tails is not None else [0] * len(tensors)
+    if len(tails) != len(tensors):
+        raise RuntimeError("tails: expected one entry per tensor")
+    srcs = []
+    for i, x in enumerate(tensors):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != keep.device:
+            raise RuntimeError(f"tensors[{i}] must be a CUDA tensor on the device of keep")
+        if x.dim() < 1 or x.shape[0] != N:
+            raise RuntimeError(f"tensors[{i}]: expected {N} rows but found {list(x.shape)}")
+        x = x.detach().contiguous()
+        rb = x.element_size() * (x.numel() // N if N else math.prod(x.shape[1:]))
+        if rb <= 0 or rb % 4:
+            raise RuntimeError(f"tensors[{i}]: a row must be a positive multiple of 4 bytes, found {rb}")
+        t = tails[i]
+        if isinstance(t, torch.Tensor):
+            if t.dtype != x.dtype or t.device != x.device or t.shape[1:] != x.shape[1:]:
+                raise RuntimeError(f"tails[{i}] must match tensors[{i}] in dtype, device and row shape")
+            t = t.detach().contiguous()
+        srcs.append((x, rb, t))
+    L = _lib()
+    dev = keep.device
+    n_keep = int(keep.count_nonzero()) if N else 0
+    with torch.cuda.device(dev):
+        nbytes = L.gsr_rows_compact_scratch_bytes(N)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        table = (RowsTensor * len(srcs))()
+        outs, n = [], 0
+        for x, rb, t in srcs:
+            nt = t.shape[0] if isinstance(t, torch.Tensor) else int(t or 0)
+            out = torch.empty((n_keep + nt,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
+            outs.append(out)
+            if out.numel():                                      # nothing kept and no tail: nothing to write
+                table[n] = RowsTensor(x.data_ptr() if N else None, out.data_ptr(), t.data_ptr() if isinstance(t, torch.Tensor) and nt else None, rb, nt)
+                n += 1
+        check(L.gsr_rows_compact_multi(N, ptr(keep) if N else None, n, table, ptr(scratch), nbytes, stream_ptr(dev)), "rows_compact_multi")
+    return outs
+
+
+@torch.no_grad()
+def adjust_anchor_(model, check_interval=100, success_threshold=0.8, grad_threshold=0.0002, min_opacity=0.005, rand=None):
+    """ScaffoldGaussian.adjust_anchor on the device, for any object with the reference's attributes (_anchor, _offset, _anchor_feat, _opacity,
+    _scaling, _rotation, get_scaling, optimizer, opacity_accum, anchor_demon, offset_gradient_accum, offset_denom, n_offsets, voxel_size,
+    update_depth, update_init_factor, update_hierachy_factor, max_radii2D).  Grows (every level), prunes, carries the Adam moments
+    (gsrast.optim.Adam or torch.optim.Adam: same state keys, `step` untouched) and resets the statistics; returns the number of anchors."""
+    for name in list(PARAM_ATTRS.values()) + ["get_scaling", "optimizer", "opacity_accum", "anchor_demon", "offset_gradient_accum", "offset_denom", "n_offsets",
+                                              "voxel_size", "update_depth", "update_init_factor", "update_hierachy_factor"]:
+        if not hasattr(model, name):
+            raise RuntimeError(f"model: attribute {name} is missing")
+    k = int(model.n_offsets)
+    anchor = _f32(model._anchor, "model._anchor", (None, 3))
+    N0 = anchor.shape[0]
+    dev = anchor.device
+    shapes = {"_offset": (N0, k, 3), "_anchor_feat": (N0, None), "_opacity": (N0, 1), "_scaling": (N0, 6), "_rotation": (N0, 4),
+              "opacity_accum": (N0, 1), "anchor_demon": (N0, 1), "offset_gradient_accum": (N0 * k, 1), "offset_denom": (N0 * k, 1)}
+    for name, shp in shapes.items():
+        _f32(getattr(model, name), "model." + name, shp)
+    scaling = model.get_scaling() if callable(model.get_scaling) else model.get_scaling
+    scaling = _f32(scaling, "model.get_scaling", (N0, None))
+    groups = {}
+    for g in model.optimizer.param_groups:
+        gname = g.get("name", "")
+        if any(s in gname for s in _SKIP):
+            continue
+        if gname not in PARAM_ATTRS or len(g["params"]) != 1:
+            raise RuntimeError(f"model.optimizer: param group '{gname}' is not one of {sorted(PARAM_ATTRS)} with a single tensor")
+        if g["params"][0] is not getattr(model, PARAM_ATTRS[gname]):
+            raise RuntimeError(f"model.optimizer: param group '{gname}' does not hold model.{PARAM_ATTRS[gname]}")
+        groups[gname] = g
+    missing = sorted(set(PARAM_ATTRS) - set(groups))
+    if missing:
+        raise RuntimeError(f"model.optimizer: no param group named {missing}")
+
+    # 1. statistics -> per-slot gradient and the slots that were seen often enough
+    grads = model.offset_gradient_accum / model.offset_denom
+    grads = torch.where(grads.isnan(), torch.zeros_like(grads), grads).abs().reshape(-1)
+    offset_mask = (model.offset_denom > check_interval * success_threshold * 0.5).reshape(-1)
+    # 2. growing
+    d = anchor_growing(anchor, model._offset, scaling, model._anchor_feat, grads, offset_mask, grad_threshold, voxel_size=model.voxel_size, n_offsets=k,
+                       update_depth=model.update_depth, update_init_factor=model.update_init_factor, update_hierachy_factor=model.update_hierachy_factor,
+                       rand=rand)
+    U = d["anchor"].shape[0]
+    # 3. - 5. reset the consumed statistics, prune mask
+    om = offset_mask.reshape(-1, 1)
+    model.offset_denom.masked_fill_(om, 0.0)
+    model.offset_gradient_accum.masked_fill_(om, 0.0)
+    anchors_mask = model.anchor_demon > check_interval * success_threshold
+    prune = (model.opacity_accum < min_opacity * model.anchor_demon) & anchors_mask
+    model.opacity_accum.masked_fill_(anchors_mask, 0.0)
+    model.anchor_demon.masked_fill_(anchors_mask, 0.0)
+    keep = ~prune.reshape(-1)
+    # 6. one compaction + append pass: [old[keep] ; new]
+    names = list(groups)
+    tensors, tails, slots = [], [], []
+    for n in names:
+        p = groups[n]["params"][0]
+        tensors.append(p); tails.append(d[n]); slots.append(("param", n))
+        st = model.optimizer.state.get(p, None)
+        if st is not None and "exp_avg" in st:
+            for key in ("exp_avg", "exp_avg_sq"):
+                tensors.append(st[key]); tails.append(U); slots.append((key, n))
+    for n in ("opacity_accum", "anchor_demon"):
+        tensors.append(getattr(model, n)); tails.append(U); slots.append(("attr", n))
+    for n in ("offset_gradient_accum", "offset_denom"):
+        tensors.append(getattr(model, n).reshape(N0, k)); tails.append(U); slots.append(("attr_k", n))
+    outs = rows_compact(keep, tensors, tails)
+    # 7. fresh parameters, carried optimizer state
+    new_state = {n: {} for n in names}
+    for (kind, n), out in zip(slots, outs):
+        if kind == "param":
+            new_state[n]["param"] = out
+        elif kind in ("exp_avg", "exp_avg_sq"):
+            new_state[n][kind] = out
+        elif kind == "attr":
+            setattr(model, n, out)
+        else:
+            setattr(model, n, out.reshape(-1, 1))
+    for n in names:
+        g = groups[n]
+        old = g["params"][0]
+        data = new_state[n]["param"]
+        if n == "scaling":
+            data[:, 3:].clamp_(max=0.05)                         # 8. scaffold_gaussian.py:527-531, on the raw parameter
+        new = torch.nn.Parameter(data.requires_grad_(True))
+        st = model.optimizer.state.get(old, None)
+        if st is not None:
+            if "exp_avg" in st:
+                st["exp_avg"] = new_state[n]["exp_avg"]; st["exp_avg_sq"] = new_state[n]["exp_avg_sq"]
+            del model.optimizer.state[old]
+            model.optimizer.state[new] = st
+        g["params"][0] = new
+        setattr(model, PARAM_ATTRS[n], new)
+    # 9.
+    Na = model._anchor.shape[0]
+    model.max_radii2D = torch.zeros(Na, dtype=torch.float32, device=dev)
+    return Na

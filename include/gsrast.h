@@ -430,6 +430,51 @@ int gsr_loss_plane_mv_scale(size_t n_depth, size_t n_near, size_t n_am, const fl
                             const float* stats, float lambda_geo, float lambda_ncc, const float* up_geo, const float* up_ncc,
                             const float* add_depth, const float* add_am, const float* up_add, int32_t have_add,
                             float* o_depth, float* o_near, float* o_am, void* stream);
+/* ---- densification geometry of the anchor models (no ABI bump: additions only).
+ * One growing level of ScaffoldGaussian.anchor_growing (gssr/gaussian/scaffold_gaussian.py:555-649), general enough for the loop body of
+ * OctreeGaussian.anchor_growing (octree_gaussian.py:401-534).  anchor [Na,3]: the first N0 are the original anchors and own the N0*k candidate
+ * slots; the rest were added at earlier levels and only occupy cells.  mask [N0] bytes or NULL: the slots of anchor a may be candidates, and its
+ * cell counts as occupied, only where mask[a] != 0 (anchors >= N0 always occupy).  Slot j of anchor a = j / k is a candidate iff
+ *   thr_lo <= grads[j] < thr_hi  and  offset_mask[j]  and  (rand == NULL or rand[j] > rand_thr)  and  the mask admits a;
+ * its point is p = anchor[a] + offset[j] * scaling[a,:3] (a multiply, then an add) and its cell c = rint((p - origin) / cell) (round-half-even,
+ * IEEE division), all in float32 with every operation rounded on its own.  Result: the distinct candidate cells that hold no admitted anchor,
+ * in lexicographic signed (x, y, z) order (torch.unique(dim=0)); new_anchor = float(c) * cell + origin; new_feat [.,F] = the element-wise maximum
+ * of anchor_feat[a] over the candidate slots of the cell (torch_scatter.scatter_max).  Bitwise deterministic.
+ * Cells are packed 21 bits per axis: a candidate cell outside [-2^20, 2^20) sets the sticky word status_dev[1] (the library only ever sets it);
+ * it never wraps.  gsr_anchor_level_find leaves the count in status_dev[0] and its state in `scratch` (>= gsr_anchor_level_scratch_bytes, caller-owned,
+ * unmodified until the emit); the caller reads the two words (its one host synchronisation per level), sizes new_anchor [count,3] / new_feat
+ * [count,F] and calls gsr_anchor_level_emit with the same level. */
+typedef struct gsr_anchor_level {
+    int32_t Na, N0, k, F;
+    int32_t scaling_stride;           /* floats per row of scaling, >= 3 (6 for get_scaling) */
+    float thr_lo, thr_hi;             /* thr_hi = +inf for Scaffold-GS */
+    float rand_thr, cell;
+    float origin[3];                  /* 0 for Scaffold-GS, init_pos for Octree-GS */
+    const float* anchor;              /* [Na,3] */
+    const uint8_t* mask;              /* [N0] or NULL */
+    const float* offset;              /* [N0,k,3] */
+    const float* scaling;             /* [N0,scaling_stride], activated */
+    const float* anchor_feat;         /* [N0,F] */
+    const float* grads;               /* [N0*k] */
+    const uint8_t* offset_mask;       /* [N0*k] */
+    const float* rand;                /* [N0*k] uniform draws, or NULL */
+} gsr_anchor_level;
+size_t gsr_anchor_level_scratch_bytes(int32_t Na, int32_t N0, int32_t k);
+int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[2]*/, void* stream);
+int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scratch, size_t scratch_bytes, uint32_t count, float* new_anchor /*[count,3]*/,
+                          float* new_feat /*[count,F]*/, void* stream);
+/* Row compaction + append for `count` tensors that share one keep mask over N rows, in one copy launch per 24 tensors (in the manner of
+ * gsr_adam_step_multi): dst = [src[keep] ; tail], tail == NULL meaning n_tail rows of zeros.  Replaces the reference's per-tensor x[mask] + cat
+ * (_prune_anchor_optimizer / cat_tensors_to_optimizer, scaffold_gaussian.py:460-541) over parameters, Adam moments and accumulators; the
+ * keep -> position scan runs once.  `t` is a HOST array; row_bytes a multiple of 4 (16- / 8-byte copies where sizes and pointers allow);
+ * dst holds (number kept + n_tail) rows and must not overlap src. */
+typedef struct gsr_rows_tensor {
+    const void* src; void* dst; const void* tail;
+    int64_t row_bytes, n_tail;
+} gsr_rows_tensor;
+size_t gsr_rows_compact_scratch_bytes(int64_t N);
+int gsr_rows_compact_multi(int64_t N, const uint8_t* keep /*[N]*/, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
+                           void* stream);
 size_t gsr_dist2_scratch_bytes(int32_t P);
 int gsr_dist2(int32_t P, const float* points /*[P,3]*/, float* out /*[P]*/, void* scratch, size_t scratch_bytes,
               void* stream);
