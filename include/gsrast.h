@@ -475,6 +475,59 @@ typedef struct gsr_rows_tensor {
 size_t gsr_rows_compact_scratch_bytes(int64_t N);
 int gsr_rows_compact_multi(int64_t N, const uint8_t* keep /*[N]*/, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
                            void* stream);
+/* ---- densify / clone / split / prune of the explicit Gaussians (3DGS, 2DGS, PGSR; no ABI bump: additions only).
+ * VanillaGaussian.densify_and_prune (gssr/gaussian/vanilla_gaussian.py:295-426), TwoDGaussian.densify_and_split (twod_gaussian.py:22-46) and
+ * PGSRGaussian.densify_and_prune (pgsr_gaussian.py:43-155) as one classification pass and one copy pass.  Per original Gaussian i of P:
+ *   g = accum[i] / denom[i] (IEEE division, NaN -> 0);  ms = max_c scaling[i,c] over the ACTIVATED scaling [P,scaling_cols], scaling_cols 2 or 3;
+ *   clone  = |g| >= clone_thr and ms <= dense_thr      (GSR_DEN_CLONE_CAP: (that ? g : 0) >  clone_cap instead);
+ *   split  =  g  >= split_thr and ms >  dense_thr      (GSR_DEN_SPLIT_CAP: (that ? g : 0) >  split_cap instead, and no abs rule);
+ *   abs rule (accum_abs != NULL): v = (not split and ms > dense_thr and max_radii2D[i] > abs_radii_thr) ? accum_abs[i] / denom_abs[i] : 0;
+ *            split |= v >= abs_thr                     (GSR_DEN_ABS_CAP: v > abs_cap instead);
+ *   pruned = opacity[i] < min_opacity or (GSR_DEN_SIZE_PRUNE and ms > world_thr); a child is pruned with ms / child_div in the place of ms.
+ * The radius term of the reference's final prune compares the zeros its densification_postfix has just allocated and never fires: it is not
+ * evaluated.  Output rows: [originals neither split nor pruned][clones of unpruned originals][children, repetition 0][repetition 1]...[N - 1],
+ * each part in index order.  gsr_densify_plan leaves in status_dev (the caller's one host synchronisation):
+ *   [0] clones selected C  [1] splits selected S  [2] originals kept  [3] clones kept  [4] split parents whose children are kept
+ *   [5] splits selected by the gradient rule;   output rows = [2] + [3] + N * [4].
+ * masked_out [3,P] or NULL receives the three masked values the caps take their quantile of (clone, split, abs).  `scratch`
+ * (>= gsr_densify_plan_scratch_bytes, caller-owned) holds the output-row -> source-row map and must stay unmodified until the emit. */
+enum { GSR_DEN_SIZE_PRUNE = 1, GSR_DEN_CLONE_CAP = 2, GSR_DEN_SPLIT_CAP = 4, GSR_DEN_ABS_CAP = 8 };
+typedef struct gsr_densify_args {
+    int32_t P, scaling_cols, N, flags;
+    float clone_thr, split_thr, abs_thr, dense_thr, min_opacity, world_thr, abs_radii_thr, child_div;   /* child_div = 0.8 * N */
+    float clone_cap, split_cap, abs_cap;
+    const float *accum, *denom;       /* [P] */
+    const float *accum_abs, *denom_abs; /* [P] or NULL: no abs rule */
+    const float* scaling;             /* [P,scaling_cols], activated */
+    const float* opacity;             /* [P], activated */
+    const float* max_radii2D;         /* [P]; read by the abs rule only */
+    float* masked_out;                /* [3,P] or NULL */
+} gsr_densify_args;
+size_t gsr_densify_plan_scratch_bytes(int32_t P, int32_t N);
+int gsr_densify_plan(const gsr_densify_args* a, void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[8]*/, void* stream);
+/* The copy pass, destination-driven, one launch per 24 tensors: dst row j = src row map[j]; zero_new != 0 (an Adam moment): clone and child
+ * rows are zeros and nothing is read for them.  `t` is a HOST array; row_bytes any positive multiple of 4 (16- / 8-byte units where sizes and
+ * pointers allow); dst holds counts[2] + counts[3] + N * counts[4] rows and must not overlap src.  counts: the HOST copy of status_dev.
+ * A second launch writes the computed columns when `c` is given: a child of parent i in repetition r gets
+ *   xyz = R(rotation[i] / |rotation[i]|) . (z * s) + xyz[i],  z = noise_split[r * S + (rank of i among the splits)],  s = scaling[i] (third 0 for 2 columns)
+ *   scaling = log(scaling[i] / child_div)
+ * and, where noise_clone is given (PGSR), a clone gets the same xyz from noise_clone[rank of i among the clones].  Float32, every operation
+ * rounded on its own. */
+typedef struct gsr_densify_tensor {
+    const void* src; void* dst;
+    int64_t row_bytes;
+    int32_t zero_new, pad_;
+} gsr_densify_tensor;
+typedef struct gsr_densify_compute {
+    const float* xyz;                 /* [P,3] source */
+    const float* rotation;            /* [P,4] source, not normalised */
+    float* xyz_dst;                   /* [rows,3] */
+    float* scaling_dst;               /* [rows,scaling_cols] */
+    const float* noise_split;         /* [N*S,3] */
+    const float* noise_clone;         /* [C,3] or NULL */
+} gsr_densify_compute;
+int gsr_densify_emit(const gsr_densify_args* a, const void* scratch, size_t scratch_bytes, const uint32_t* counts /*[8] host*/, int32_t count,
+                     const gsr_densify_tensor* t, const gsr_densify_compute* c, void* stream);
 size_t gsr_dist2_scratch_bytes(int32_t P);
 int gsr_dist2(int32_t P, const float* points /*[P,3]*/, float* out /*[P]*/, void* scratch, size_t scratch_bytes,
               void* stream);

@@ -1,0 +1,268 @@
+"""Densify / clone / split / prune of the explicit Gaussians on the device (gsrast.densify; gs-sr_amd/csrc/gsr_densify.hip).
+
+Copied rows, maps, counts, moments and statistics are compared for exact equality: with the fixtures the reference's own VanillaGaussian /
+TwoDGaussian / PGSRGaussian.densify_and_prune produced (tests/golden/make_golden_densify.py) and, on random scenes of up to 300 000 Gaussians,
+with the torch restatement that test_densify_cpu.py holds to those fixtures (tests/ref_densify_torch.py).  The computed columns (children's xyz
+and scaling, PGSR clones' xyz) are compared with a float64 evaluation of the reference formula on the float32 inputs:
+    |d xyz_i| <= 32 * 2^-24 * (|xyz_i| + sum_j |z_j s_j|)      (about 20 roundings on the path)
+    |d scaling| <= 8 * 2^-24 * max(1, |want|)                  (a division, a log, the output rounding)
+"""
+import numpy as np
+import pytest
+import torch
+
+import densify_cases as DC
+import ref_densify_torch as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+KINDS = {"vanilla": dict(cols=3, pgsr=False), "twod": dict(cols=2, pgsr=False), "pgsr": dict(cols=3, pgsr=True)}
+
+
+def _call(m, rules, pgsr, **kw):
+    from gsrast import densify
+    return densify.densify_and_prune_(m, rules["max_grad"], rules["min_opacity"], rules["extent"], rules["max_screen_size"],
+                                      abs_max_grad=rules["abs_max_grad"] if pgsr else None, **kw)
+
+
+def _check_model_state(m, rows, pgsr, had_state=True):
+    stats = ["xyz_gradient_accum", "denom", "max_radii2D"] + (["xyz_gradient_accum_abs", "denom_abs", "max_weight"] if pgsr else [])
+    for k in stats:
+        v = getattr(m, k)
+        assert v.shape == ((rows,) if k in ("max_radii2D", "max_weight") else (rows, 1)) and v.dtype == torch.float32 and v.is_cuda and not v.any(), k
+    assert len(m.optimizer.state) == (6 if had_state else 0)
+    for g in m.optimizer.param_groups:
+        q = getattr(m, DC.ATTRS[g["name"]])
+        assert g["params"][0] is q and isinstance(q, torch.nn.Parameter) and q.is_leaf and q.requires_grad and q.shape[0] == rows and q.is_contiguous()
+        if had_state:
+            st = m.optimizer.state[q]
+            assert float(st["step"]) == 7.0 and st["exp_avg"].shape == q.shape and st["exp_avg_sq"].shape == q.shape
+
+
+def _step(m, rows):
+    for g in m.optimizer.param_groups:
+        q = g["params"][0]
+        q.grad = torch.full_like(q, 0.25)
+    m.optimizer.step()
+    torch.cuda.synchronize()
+    for g in m.optimizer.param_groups:
+        st = m.optimizer.state[g["params"][0]]
+        assert float(st["step"]) == 8.0
+        if g["params"][0].numel():
+            assert torch.isfinite(st["exp_avg"]).all() and torch.isfinite(st["exp_avg_sq"]).all() and st["exp_avg"].shape[0] == rows
+
+
+@pytest.mark.parametrize("opt", ["gsrast", "torch"])
+@pytest.mark.parametrize("case", DC.FIXTURES)
+def test_fixture(case, opt):
+    d = DC.load_fixture(case)
+    p, mom, stats, pgsr, rules = DC.fixture_inputs(d)
+    act = (torch.tensor(d["scaling_act"], device=DEV), torch.tensor(d["opacity_act"], device=DEV))   # as the reference computed them
+    kw = dict(max_all_points=rules["max_all_points"], max_abs_split_points=rules["max_abs_split_points"]) if pgsr else {}
+    m = DC.Model(p, mom, stats, DEV, optimizer=opt, pgsr=pgsr, activated=act, **kw)
+    C, S, pruned, rows = (int(v) for v in d["counts"])
+    n = _call(m, rules, pgsr, noise_split=torch.tensor(d["z_split"], device=DEV), noise_clone=torch.tensor(d["z_clone"], device=DEV) if pgsr else None)
+    assert n == rows
+    _check_model_state(m, rows, pgsr)
+    L = DC.run_layout(p, mom, stats, d["scaling_act"], d["opacity_act"], d["z_split"], d["z_clone"], pgsr, rules)
+    assert L["counts"]["rows"] == rows
+    got_p = {k: v.cpu() for k, v in m.tensors().items()}
+    got_m = {k: (a.cpu(), b.cpu()) for k, (a, b) in m.moments().items()}
+    worst = DC.check_against_layout(got_p, got_m, L, p, d["scaling_act"], d["z_split"], d["z_clone"], pgsr, what=case)
+    print(case, opt, "worst error in units of the bounds (xyz, scaling):", worst)
+    # directly against the reference's output: every copied row, bit for bit
+    n_o, n_c, n_s = L["parts"]
+    for k in DC.NAMES:
+        lim = rows if k not in ("xyz", "scaling") else (n_o if (k == "xyz" and pgsr) else n_o + n_c)
+        assert torch.equal(got_p[k][:lim], torch.tensor(d["out_" + k])[:lim]), k
+        assert torch.equal(got_m[k][0], torch.tensor(d["out_m_" + k])) and torch.equal(got_m[k][1], torch.tensor(d["out_v_" + k])), k
+    _step(m, rows)
+
+
+def _random_model(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), **kw):
+    spec = KINDS[kind]
+    p, mom, stats = DC.make_inputs(P, seed, cols=spec["cols"], rest=rest, pgsr=spec["pgsr"], device=DEV, frac=frac)
+    m = DC.Model(p, mom, stats, DEV, optimizer=opt, pgsr=spec["pgsr"], with_state=with_state, **kw)
+    return m, p, mom, stats
+
+
+def _noise(m, stats, pgsr, rules, seed):
+    kw = dict(accum_abs=m.xyz_gradient_accum_abs, denom_abs=m.denom_abs, max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points) if pgsr else {}
+    clone, split, _, _ = R.classify(m.xyz_gradient_accum, m.denom, m.get_scaling.detach(), m.get_opacity.detach(), m.max_radii2D, **rules, **kw)
+    g = torch.Generator(device=DEV); g.manual_seed(seed)
+    return torch.randn(2 * int(split.sum()), 3, device=DEV, generator=g), torch.randn(int(clone.sum()), 3, device=DEV, generator=g)
+
+
+def _rules(pgsr, max_screen_size=20, **kw):
+    r = dict(DC.RULES, max_screen_size=max_screen_size)
+    if pgsr:
+        r.update(DC.ABS_RULES)
+    r.update(kw)
+    return r
+
+
+def _run_random(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), rules_kw=None, **model_kw):
+    pgsr = KINDS[kind]["pgsr"]
+    rules = _rules(pgsr, **(rules_kw or {}))
+    m, p, mom, stats = _random_model(kind, P, seed, opt, with_state, rest, frac, **model_kw)
+    s_act, o_act = m.get_scaling.detach().clone(), m.get_opacity.detach().clone()
+    z_split, z_clone = _noise(m, stats, pgsr, rules, seed)
+    lay_rules = dict(rules)
+    if pgsr:
+        lay_rules.update(max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points)
+    L = DC.run_layout(p, mom if with_state else {}, stats, s_act, o_act, z_split, z_clone, pgsr, lay_rules, device=DEV)
+    n = _call(m, rules, pgsr, noise_split=z_split, noise_clone=z_clone if pgsr else None)
+    assert n == L["counts"]["rows"]
+    _check_model_state(m, n, pgsr, had_state=with_state)
+    worst = DC.check_against_layout(m.tensors(), m.moments(), L, p, s_act, z_split, z_clone, pgsr, what=f"{kind} P={P}")
+    return m, L, worst
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+@pytest.mark.parametrize("P", [300_000, 77_777])
+def test_random_scene_equals_restatement(kind, P):
+    m, L, worst = _run_random(kind, P, seed=P % 1000 + len(kind))
+    c = L["counts"]
+    print(kind, P, c, "worst error in units of the bounds (xyz, scaling):", worst)
+    assert c["clones"] > 0.05 * P and c["splits"] > 0.05 * P and c["pruned"] > 0.02 * P
+    m2, _, _ = _run_random(kind, P, seed=P % 1000 + len(kind))                      # a repeated call gives the same bytes
+    for k in DC.NAMES:
+        assert torch.equal(m.tensors()[k], m2.tensors()[k]), k
+        assert torch.equal(m.moments()[k][0], m2.moments()[k][0]) and torch.equal(m.moments()[k][1], m2.moments()[k][1]), k
+    _step(m, c["rows"])
+
+
+def test_pgsr_caps_on_a_random_scene():
+    """max_all_points binds in the split, then (another scene) max_abs_split_points binds: quantile thresholds taken on the device."""
+    P = 50_000
+    m, L, _ = _run_random("pgsr", P, seed=5, max_all_points=P + 9000)
+    assert L["counts"]["rows"] <= P + 9000 and L["counts"]["splits"] > 0
+    m, L, _ = _run_random("pgsr", P, seed=6, max_abs_split_points=100)
+    assert L["counts"]["splits"] > 100
+
+
+@pytest.mark.parametrize("opt", ["gsrast", "torch"])
+def test_groups_without_state_stay_without_state(opt):
+    m, L, _ = _run_random("vanilla", 5000, seed=3, opt=opt, with_state=False, rest=3)
+    assert len(m.optimizer.state) == 0 and m.moments() == {}
+
+
+def test_generated_noise_and_wrong_noise_length():
+    from gsrast import densify
+    rules = _rules(True)
+    m, p, mom, stats = _random_model("pgsr", 4000, 9, rest=3)
+    z_split, z_clone = _noise(m, stats, True, rules, 1)
+    with pytest.raises(RuntimeError, match=f"noise_split: expected {z_split.shape[0]} rows"):
+        _call(m, rules, True, noise_split=z_split[:-2], noise_clone=z_clone)
+    with pytest.raises(RuntimeError, match=f"noise_clone: expected {z_clone.shape[0]} rows"):
+        _call(m, rules, True, noise_split=z_split, noise_clone=z_clone[:-1])
+    assert m._xyz.shape[0] == 4000                                            # nothing was installed
+    g = torch.Generator(device=DEV); g.manual_seed(11)
+    n1 = _call(m, rules, True, generator=g)
+    m2, _, _, _ = _random_model("pgsr", 4000, 9, rest=3)
+    g.manual_seed(11)
+    n2 = _call(m2, rules, True, generator=g)
+    assert n1 == n2 and torch.equal(m._xyz, m2._xyz) and torch.isfinite(m._xyz).all() and torch.isfinite(m._scaling).all()
+    m3, _, _, _ = _random_model("pgsr", 4000, 9, rest=3)
+    _call(m3, rules, True)                                                    # default generator
+    assert m3._xyz.shape == m._xyz.shape and not torch.equal(m3._xyz, m._xyz)
+    with pytest.raises(RuntimeError, match="CUDA tensor"):
+        _call(m3, rules, True, noise_split=torch.zeros(2, 3))
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_edge_cases(kind):
+    pgsr = KINDS[kind]["pgsr"]
+    # P = 0
+    m, L, _ = _run_random(kind, 0, seed=1, rest=3)
+    assert m._xyz.shape == (0, 3) and m._features_rest.shape == (0, 3, 3)
+    # nothing selected, nothing pruned: the tensors come back equal
+    m, L, _ = _run_random(kind, 3000, seed=2, rest=3, frac=(0.0, 0.0, 0.0))
+    assert L["counts"] == {"clones": 0, "splits": 0, "pruned": 0, "rows": 3000}
+    # everything pruned
+    m, L, _ = _run_random(kind, 3000, seed=3, rest=3, rules_kw=dict(min_opacity=2.0))
+    assert L["counts"]["rows"] == 0 and m._xyz.shape == (0, 3) and m._scaling.shape == (0, KINDS[kind]["cols"])
+    # P around the block size of the scan (1024) and of a wave (64)
+    for P in (1, 63, 1023, 1025, 2049):
+        _run_random(kind, P, seed=P, rest=3)
+    # degree 0: an f_rest of zero width keeps its shape
+    m, L, _ = _run_random(kind, 2000, seed=4, rest=0)
+    assert m._features_rest.shape == (L["counts"]["rows"], 0, 3)
+    # more children than two
+    from gsrast import densify
+    m, p, mom, stats = _random_model(kind, 1500, 8, rest=3)
+    rules = _rules(pgsr)
+    n = densify.densify_and_prune_(m, rules["max_grad"], rules["min_opacity"], rules["extent"], None, abs_max_grad=rules["abs_max_grad"] if pgsr else None, N=3)
+    assert n == m._xyz.shape[0] and torch.isfinite(m._xyz).all()
+
+
+def test_reset_opacity():
+    from gsrast import densify
+    for opt in ("gsrast", "torch"):
+        m, p, mom, stats = _random_model("vanilla", 3000, 12, opt=opt, rest=3)
+        old, act = m._opacity, m.get_opacity.detach().clone()
+        x = torch.min(act, torch.ones_like(act) * 0.01)
+        want = torch.log(x / (1 - x))
+        densify.reset_opacity_(m)
+        q = m._opacity
+        assert q is not old and isinstance(q, torch.nn.Parameter) and q.is_leaf and torch.equal(q.detach(), want)
+        assert m.optimizer.param_groups[3]["params"][0] is q and old not in m.optimizer.state and len(m.optimizer.state) == 6
+        st = m.optimizer.state[q]
+        assert float(st["step"]) == 7.0 and not st["exp_avg"].any() and not st["exp_avg_sq"].any() and st["exp_avg"].shape == q.shape
+        assert float(m.get_opacity.detach().max()) <= 0.01 * (1 + 1e-6)
+        _step(m, 3000)
+
+
+class _Grad:
+    def __init__(self, g):
+        self.grad = g
+
+
+@pytest.mark.parametrize("kind", ["vanilla", "pgsr"])
+def test_densify_schedule(kind):
+    """Which steps accumulate, densify and reset, and size_threshold None up to opacity_reset_interval (vanilla_gaussian.py:467-479)."""
+    from gsrast import densify
+    pgsr = KINDS[kind]["pgsr"]
+    P = 6000
+
+    def fresh():
+        m, p, mom, stats = _random_model(kind, P, 31, rest=3)
+        m.config = DC.config()
+        return m, p, mom, stats
+
+    def frame(m, visible):
+        n = m._xyz.shape[0]
+        kw = dict(visibility_filter=torch.full((n,), visible, dtype=torch.bool, device=DEV), radii=torch.full((n,), 77, dtype=torch.int32, device=DEV),
+                  viewspace_points=_Grad(torch.ones(n, 3, device=DEV)))
+        if pgsr:
+            kw.update(out_observe=torch.ones(n, dtype=torch.int32, device=DEV), viewspace_points_abs=_Grad(torch.ones(n, 3, device=DEV)))
+        return kw
+    # a step that only accumulates
+    m, p, mom, stats = fresh()
+    a0, d0 = m.xyz_gradient_accum.clone(), m.denom.clone()
+    assert densify.densify_(m, 450, **frame(m, True)) == {"densified": False, "reset": False}
+    assert torch.equal(m.denom, d0 + 1) and torch.allclose(m.xyz_gradient_accum, a0 + 2 ** 0.5) and float(m.max_radii2D.min()) == 77.0 and m._xyz.shape[0] == P
+    # densifying steps: nothing visible, so the statistics stay what the scene was built with
+    for step, size, reset in ((600, None, False), (3000, None, True), (3100, 20, False)):
+        m, p, mom, stats = fresh()
+        rules = _rules(pgsr, max_screen_size=size)
+        s_act, o_act = m.get_scaling.detach().clone(), m.get_opacity.detach().clone()
+        z_split, z_clone = _noise(m, stats, pgsr, rules, step)
+        L = DC.run_layout(p, mom, stats, s_act, o_act, z_split, z_clone, pgsr, dict(rules, **(dict(max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points) if pgsr else {})), device=DEV)
+        done = densify.densify_(m, step, noise_split=z_split, noise_clone=z_clone if pgsr else None, **frame(m, False))
+        assert done == {"densified": True, "reset": reset} and m._xyz.shape[0] == L["counts"]["rows"], (step, done)
+        for k in ("f_dc", "f_rest", "rotation"):
+            assert torch.equal(m.tensors()[k], L["params"][k]), (step, k)
+        if reset:
+            assert float(m.get_opacity.detach().max()) <= 0.01 * (1 + 1e-6) and not m.moments()["opacity"][0].any()
+        else:
+            assert torch.equal(m.tensors()["opacity"], L["params"]["opacity"])
+    sized = DC.run_layout(p, mom, stats, s_act, o_act, z_split, z_clone, pgsr, dict(_rules(pgsr, max_screen_size=None), **(dict(max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points) if pgsr else {})), device=DEV)
+    assert sized["counts"]["rows"] > L["counts"]["rows"]                      # the scene does hold rows that only the size rule prunes
+    # steps outside the schedule
+    m, p, mom, stats = fresh()
+    assert densify.densify_(m, 500, **frame(m, False)) == {"densified": False, "reset": False}        # step > densify_from_iter is strict
+    assert densify.densify_(m, 650, **frame(m, False)) == {"densified": False, "reset": False}
+    d0 = m.denom.clone()
+    assert densify.densify_(m, 15000, **frame(m, True)) == {"densified": False, "reset": False} and torch.equal(m.denom, d0)     # not even statistics
+    assert densify.densify_(m, 6000, **frame(m, False)) == {"densified": True, "reset": True}
