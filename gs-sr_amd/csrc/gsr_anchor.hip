@@ -9,55 +9,13 @@
 //
 // This unit is built with -ffp-contract=off: the cell of a point is an integer output and must not depend on FMA contraction.
 #include "gsr_common.h"
+#include "gsr_scan.h"
+#include <vector>
 
 #define ANC_BLOCK 1024
 #define ANC_BIAS 1048576            // 2^20: cells in [-2^20, 2^20 - 1] per axis
 #define ANC_CNT_ENTRIES 0           // counters: entries in the sort
 #define ANC_CNT_HEADS 1             //           new anchors
-
-__device__ __forceinline__ uint32_t anc_wave_incl_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if ((int)lane >= d) v += t;
-    }
-    return v;
-}
-// block-wide exclusive scan over blockDim.x <= 1024 threads; *total = block sum.  lds: 17 words
-__device__ __forceinline__ uint32_t anc_block_excl_scan(uint32_t v, uint32_t* lds, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    const uint32_t s = anc_wave_incl_scan(v);
-    if (lane == 63) lds[wave] = s;
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t w = (lane < nw) ? lds[lane] : 0;
-        const uint32_t ws = anc_wave_incl_scan(w);
-        if (lane < nw) lds[lane] = ws - w;
-        if (lane == nw - 1) lds[16] = ws;
-    }
-    __syncthreads();
-    const uint32_t r = s - v + lds[wave];
-    *total = lds[16];
-    __syncthreads();
-    return r;
-}
-
-// in-place exclusive scan of the n block sums by ONE block; the total goes to *total_out
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_scan_sums(uint32_t* __restrict__ sums, uint32_t n, uint32_t* __restrict__ total_out)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t chunk = (n + ANC_BLOCK - 1) / ANC_BLOCK;
-    const uint32_t b = min(n, threadIdx.x * chunk), e = min(n, b + chunk);
-    uint32_t sum = 0;
-    for (uint32_t i = b; i < e; i++) sum += sums[i];
-    uint32_t tot;
-    uint32_t run = anc_block_excl_scan(sum, lds, &tot);
-    for (uint32_t i = b; i < e; i++) { const uint32_t v = sums[i]; sums[i] = run; run += v; }
-    if (threadIdx.x == 0) *total_out = tot;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- entries of a level
 // c = rint((p - origin) / cell): round-half-even, IEEE division (no reciprocal), every operation rounded on its own
@@ -104,7 +62,7 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_count(gsr_anchor_level 
     uint64_t key;
     const uint32_t f = (i < cap && anc_entry(i, L, &key, status)) ? 1u : 0u;
     uint32_t tot;
-    anc_block_excl_scan(f, lds, &tot);
+    block_excl_scan(f, lds, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -117,7 +75,7 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_place(gsr_anchor_level 
     uint64_t key = 0;
     const bool f = i < cap && anc_entry(i, L, &key, status);
     uint32_t tot;
-    const uint32_t pos = sums[blockIdx.x] + anc_block_excl_scan(f ? 1u : 0u, lds, &tot);       // < cap: at most one position per entry
+    const uint32_t pos = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);       // < cap: at most one position per entry
     if (f) { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
 }
 
@@ -145,7 +103,7 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_count(const uint32_t* __
     __shared__ uint32_t lds[17];
     const uint32_t f = anc_is_head(blockIdx.x * ANC_BLOCK + threadIdx.x, *n_dev, hi, perm, key_lo) ? 1u : 0u;
     uint32_t tot;
-    anc_block_excl_scan(f, lds, &tot);
+    block_excl_scan(f, lds, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -156,7 +114,7 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_place(const uint32_t* __
     const uint32_t p = blockIdx.x * ANC_BLOCK + threadIdx.x;
     const bool f = anc_is_head(p, *n_dev, hi, perm, key_lo);
     uint32_t tot;
-    const uint32_t q = sums[blockIdx.x] + anc_block_excl_scan(f ? 1u : 0u, lds, &tot);        // q <= p < capacity
+    const uint32_t q = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);        // q <= p < capacity
     if (f) head_pos[q] = p;
 }
 
@@ -249,7 +207,7 @@ extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, 
     if (cap) {
         const uint32_t nblk = gsr_div_up(cap, ANC_BLOCK);
         hipLaunchKernelGGL(k_anc_entry_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev);
-        hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, a.sums, nblk, a.counters + ANC_CNT_ENTRIES);
+        gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_ENTRIES, nullptr, s);
         hipLaunchKernelGGL(k_anc_entry_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev, a.key_lo, a.key_hi, a.ka, a.src);
         const uint32_t* n_dev = a.counters + ANC_CNT_ENTRIES;
         uint32_t *k0 = a.ka, *v0 = a.va, *k1 = a.kb, *v1 = a.vb;
@@ -262,7 +220,7 @@ extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, 
         // both sorts run 4 passes of 8 bits: the order ends in (ka, va), the run heads go to kb -- gsr_anchor_level_emit relies on it
         if (k0 != a.ka || v0 != a.va) { gsr_set_error("anchor_level_find: unexpected sort buffer parity"); return 1; }
         hipLaunchKernelGGL(k_anc_head_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums);
-        hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, a.sums, nblk, a.counters + ANC_CNT_HEADS);
+        gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_HEADS, nullptr, s);
         hipLaunchKernelGGL(k_anc_head_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums, a.kb);
     }
     hipLaunchKernelGGL(k_anc_publish, dim3(1), dim3(64), 0, s, a.counters, status_dev);
@@ -288,69 +246,33 @@ extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scr
 
 // ---------------------------------------------------------------------------------------------------------------- rows: compact + append
 // dst = [src[keep] ; tail] for many tensors that share one keep mask over N rows (the reference's per-tensor x[mask] + cat over six parameters,
-// twelve Adam moments and four accumulators: ~60 launches and a nonzero() synchronisation each).  The keep -> position scan runs once.
-#define GSR_ROWS_MAX 24
-#define GSR_ROWS_CHUNK 2048          // copy units per block
-struct RowsEntry { const char* src; char* dst; const char* tail; uint64_t units_keep, units_all; uint32_t upr, ulog, first_block, pad_; };   // upr: units per row
-struct RowsTable { int32_t count; RowsEntry e[GSR_ROWS_MAX]; };
-
+// twelve Adam moments and four accumulators: ~60 launches and a nonzero() synchronisation each).  The keep -> position scan runs once and leaves
+// map[position] = row for every kept row; the row mover (gsr_rows.hip) does the rest, with the number kept read on the device.
 __global__ void __launch_bounds__(ANC_BLOCK) k_rows_count(const uint8_t* __restrict__ keep, uint32_t N, uint32_t* __restrict__ sums)
 {
     __shared__ uint32_t lds[17];
     const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
     uint32_t tot;
-    anc_block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
+    block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
-__global__ void __launch_bounds__(ANC_BLOCK) k_rows_pos(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ pos)
+__global__ void __launch_bounds__(ANC_BLOCK) k_rows_map(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ map)
 {
     __shared__ uint32_t lds[17];
     const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    const bool f = i < N && keep[i];
     uint32_t tot;
-    const uint32_t p = sums[blockIdx.x] + anc_block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
-    if (i < N) pos[i] = p;
+    const uint32_t p = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);          // p <= i < N
+    if (f) map[p] = i;
 }
 
-template <typename T>
-__device__ __forceinline__ void rows_copy(const RowsEntry& E, uint64_t base, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ pos, uint32_t n_keep)
-{
-    const T* src = reinterpret_cast<const T*>(E.src);
-    const T* tail = reinterpret_cast<const T*>(E.tail);
-    T* dst = reinterpret_cast<T*>(E.dst);
-    const uint64_t end = min(E.units_all, base + GSR_ROWS_CHUNK);
-    T zero;
-    memset(&zero, 0, sizeof(T));
-    for (uint64_t u = base + threadIdx.x; u < end; u += 256) {
-        if (u < E.units_keep) {
-            const uint32_t r = (uint32_t)(u / E.upr), c = (uint32_t)(u - (uint64_t)r * E.upr);
-            if (keep[r]) dst[(uint64_t)pos[r] * E.upr + c] = src[u];
-        } else {
-            const uint64_t v = u - E.units_keep;
-            dst[(uint64_t)n_keep * E.upr + v] = tail ? tail[v] : zero;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_rows_compact(RowsTable T, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ n_keep_dev)
-{
-    int k = 0;
-#pragma unroll 1
-    for (int i = 1; i < T.count; i++) k = (blockIdx.x >= T.e[i].first_block) ? i : k;
-    const RowsEntry& E = T.e[k];
-    const uint64_t base = (uint64_t)(blockIdx.x - E.first_block) * GSR_ROWS_CHUNK;
-    const uint32_t n_keep = *n_keep_dev;
-    if (E.ulog == 4) rows_copy<uint4>(E, base, keep, pos, n_keep);
-    else if (E.ulog == 3) rows_copy<uint2>(E, base, keep, pos, n_keep);
-    else rows_copy<uint32_t>(E, base, keep, pos, n_keep);
-}
-
-struct RowsScratch { uint32_t *sums, *pos, *count; size_t bytes; };
+struct RowsScratch { uint32_t *sums, *map, *count; size_t bytes; };
 static RowsScratch rows_carve(uint32_t N, void* base)
 {
     RowsScratch r; char* p = (char*)base;
     const size_t n = N > 0 ? N : 1;
     auto take = [&](size_t bytes) { char* q = p; p += gsr_align(bytes); return (uint32_t*)q; };
-    r.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4); r.pos = take(n * 4); r.count = take(64);
+    r.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4); r.map = take(n * 4); r.count = take(64);
     r.bytes = (size_t)(p - (char*)base);
     return r;
 }
@@ -363,40 +285,20 @@ extern "C" size_t gsr_rows_compact_scratch_bytes(int64_t N)
 extern "C" int gsr_rows_compact_multi(int64_t N, const uint8_t* keep, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
                                       void* stream)
 {
-    if (N < 0 || N >= (1ll << 31)) { gsr_set_error("rows_compact_multi: N=%lld out of range", (long long)N); return 1; }
-    if (N > 0 && !keep) { gsr_set_error("rows_compact_multi: keep is NULL"); return 1; }
-    if (count < 0 || (count > 0 && !t)) { gsr_set_error("rows_compact_multi: bad table"); return 1; }
+    const char* who = "rows_compact_multi";
+    if (N < 0 || N >= (1ll << 31)) { gsr_set_error("%s: N=%lld out of range", who, (long long)N); return 1; }
+    if (N > 0 && !keep) { gsr_set_error("%s: keep is NULL", who); return 1; }
     const RowsScratch r = rows_carve((uint32_t)N, scratch);
-    if (!scratch || r.bytes > scratch_bytes) { gsr_set_error("rows_compact_multi: scratch too small: %zu < %zu", scratch_bytes, r.bytes); return 1; }
-    for (int32_t i = 0; i < count; i++) {
-        const gsr_rows_tensor& a = t[i];
-        if (a.row_bytes <= 0 || (a.row_bytes & 3) || a.n_tail < 0) { gsr_set_error("rows_compact_multi: tensor %d: row_bytes must be a positive multiple of 4, n_tail >= 0", i); return 1; }
-        if (!a.dst || (N > 0 && !a.src)) { gsr_set_error("rows_compact_multi: tensor %d: null pointer", i); return 1; }
-        if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.tail) & 3) { gsr_set_error("rows_compact_multi: tensor %d: pointers must be 4-byte aligned", i); return 1; }
-    }
+    if (!scratch || r.bytes > scratch_bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, r.bytes); return 1; }
+    std::vector<gsr_rows_item> items;
+    for (int32_t i = 0; t && i < count; i++) items.push_back({t[i].src, t[i].dst, t[i].tail, t[i].row_bytes, t[i].n_tail, false});
+    const gsr_rows_map m = {r.map, r.count, (uint32_t)N, 0u, (uint32_t)N};
     hipStream_t s = (hipStream_t)stream;
+    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, false, s)) return 1;                      // the checks, before anything is launched
     const uint32_t nblk = gsr_div_up((uint32_t)(N > 0 ? N : 1), ANC_BLOCK);
     hipLaunchKernelGGL(k_rows_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums);
-    hipLaunchKernelGGL(k_anc_scan_sums, dim3(1), dim3(ANC_BLOCK), 0, s, r.sums, nblk, r.count);
-    hipLaunchKernelGGL(k_rows_pos, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums, r.pos);
-    int32_t i = 0;
-    while (i < count) {
-        RowsTable T; T.count = 0;
-        uint64_t blocks = 0;
-        for (; i < count && T.count < GSR_ROWS_MAX; i++) {
-            const gsr_rows_tensor& a = t[i];
-            const uintptr_t al = (uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.tail | (uintptr_t)a.row_bytes;
-            const uint32_t ulog = (al & 15) == 0 ? 4u : ((al & 7) == 0 ? 3u : 2u);
-            RowsEntry& E = T.e[T.count];
-            E.src = (const char*)a.src; E.dst = (char*)a.dst; E.tail = (const char*)a.tail; E.ulog = ulog; E.upr = (uint32_t)(a.row_bytes >> ulog); E.pad_ = 0;
-            E.units_keep = (uint64_t)N * E.upr; E.units_all = E.units_keep + (uint64_t)a.n_tail * E.upr;
-            if (E.units_all == 0) continue;
-            E.first_block = (uint32_t)blocks;
-            blocks += (E.units_all + GSR_ROWS_CHUNK - 1) / GSR_ROWS_CHUNK;
-            if (blocks >= (1ull << 31)) { gsr_set_error("rows_compact_multi: tensor %d: too many bytes for one launch", i); return 1; }
-            T.count++;
-        }
-        if (blocks) hipLaunchKernelGGL(k_rows_compact, dim3((uint32_t)blocks), dim3(256), 0, s, T, keep, r.pos, r.count);
-    }
-    return gsr_check_launch("rows_compact_multi", s, false);
+    gsr_scan_small(r.sums, nblk, 1, 0, r.count, nullptr, s);
+    hipLaunchKernelGGL(k_rows_map, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums, r.map);
+    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, true, s)) return 1;
+    return gsr_check_launch(who, s, false);
 }

@@ -11,47 +11,19 @@
 // Stability of every pass makes the result identical to the reference's single 64-bit sort.
 #include "gsr_common.h"
 #include "gsr_tile_cull.h"
+#include "gsr_scan.h"
 
 // ------------------------------------------------------------------------------------------------ wave helpers
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
-// inclusive scan across a 64-lane wave
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d, 64);
-        if ((int)lane_id() >= d) v += t;
-    }
-    return v;
-}
-
-// block-wide inclusive scan for up to 1024 threads; returns inclusive value, *total = block sum
-__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* lds /*>=17 words*/, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    uint32_t s = wave_incl_scan(v);
-    if (lane == 63) lds[wave] = s;
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t w = (lane < nw) ? lds[lane] : 0;
-        uint32_t ws = wave_incl_scan(w);
-        if (lane < nw) lds[lane] = ws - w;        // exclusive prefix per wave
-        if (lane == nw - 1) lds[16] = ws;
-    }
-    __syncthreads();
-    s += lds[wave];
-    *total = lds[16];
-    __syncthreads();
-    return s;
-}
-
 // ------------------------------------------------------------------------------------------------ generic scan
-// in-place exclusive scan of n words by ONE block (n is small: histograms, block sums)
-__global__ void __launch_bounds__(GSR_SCAN_BLOCK) k_scan_small(uint32_t* data, uint32_t n, uint32_t* total_out, uint32_t* host_word, int total_only = 0)
+// in-place exclusive scan of n words by ONE block (n is small: histograms, block sums); block r of the launch takes row r = data + r * stride
+// and publishes its total in total_out[r] / host_word[r]
+__global__ void __launch_bounds__(GSR_SCAN_BLOCK) k_scan_small(uint32_t* data, uint32_t n, uint32_t* total_out, uint32_t* host_word, int total_only = 0,
+                                                               uint32_t stride = 0)
 {
     __shared__ uint32_t lds[17];
+    data += (size_t)blockIdx.x * stride;
     const uint32_t chunk = (n + blockDim.x - 1) / blockDim.x;
     const uint32_t b = threadIdx.x * chunk, e = min(n, b + chunk);
     uint32_t sum = 0;
@@ -62,9 +34,13 @@ __global__ void __launch_bounds__(GSR_SCAN_BLOCK) k_scan_small(uint32_t* data, u
     if (!total_only)           // total_only: the block sums stay as they are (k_duplicate adds them up itself), only the total is published
         for (uint32_t i = b; i < e; i++) { uint32_t v = data[i]; data[i] = run; run += v; }
     if (threadIdx.x == 0) {
-        if (total_out) *total_out = tot;
-        if (host_word) __hip_atomic_store(host_word, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // mapped pinned word: no D2H copy command
+        if (total_out) total_out[blockIdx.x] = tot;
+        if (host_word) __hip_atomic_store(host_word + blockIdx.x, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // mapped pinned word: no D2H copy command
     }
+}
+void gsr_scan_small(uint32_t* data, uint32_t n, uint32_t rows, uint32_t stride, uint32_t* totals, uint32_t* totals2, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scan_small, dim3(rows), dim3(GSR_SCAN_BLOCK), 0, s, data, n, totals, totals2, 0, stride);
 }
 
 // exclusive scan of every row of a [rows x cols] matrix in place, one block per row (coalesced), row totals to tot[].

@@ -169,3 +169,15 @@ static inline size_t gsr_sort_hist_words(uint32_t nblk_1024, uint32_t NB) { retu
 int gsr_radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n, const uint32_t* n_dev,
                          int begin_bit, int end_bit, int bits_per_pass, bool identity_vals, uint32_t* hist,
                          bool* result_in_b, hipStream_t s, bool big_blocks = false, bool group0_zeroed = false);
+// In-place exclusive scan of `rows` rows of n words (row r at data + r * stride), one block per row, n small (block sums): k_scan_small.  Row r's
+// total goes to totals[r] and, where given, to totals2[r] as well.
+void gsr_scan_small(uint32_t* data, uint32_t n, uint32_t rows, uint32_t stride, uint32_t* totals, uint32_t* totals2, hipStream_t s);
+
+// The row mover (gsr_rows.hip): for every tensor of a host table, one launch per 24 tensors,
+//   dst row r = src row map[r]            r < n_map         (zeros instead where zero_new and r >= n_carried; nothing is read for those)
+//             = tail row r - n_map        n_map <= r < n_map + n_tail   (zeros where tail is NULL)
+// n_map is read from *n_map_dev where that is given; n_map is then the most it can be and sizes the grid.  src has src_rows rows.
+struct gsr_rows_item { const void* src; void* dst; const void* tail; int64_t row_bytes, n_tail; bool zero_new; };
+struct gsr_rows_map { const uint32_t* map; const uint32_t* n_map_dev; uint32_t n_map, n_carried, src_rows; };
+// Checks the table (errors are prefixed with `who`), then launches unless !launch: an entry point with kernels of its own in front validates first.
+int gsr_rows_move(const char* who, const gsr_rows_map& m, int32_t count, const gsr_rows_item* t, bool launch, hipStream_t s);

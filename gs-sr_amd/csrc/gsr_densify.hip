@@ -3,11 +3,12 @@
 // The reference (VanillaGaussian.densify_and_prune, gssr/gaussian/vanilla_gaussian.py:295-426; twod_gaussian.py:22-46; pgsr_gaussian.py:43-155)
 // rebuilds all 6 parameters and 12 Adam moments four times (cat for the clones, cat for the children, a boolean gather for the split parents, a
 // boolean gather for the final prune).  Here one pass classifies every original (k_den_count / k_den_place: flags, six prefix sums, the
-// output-row -> source-row map) and one destination-driven launch writes every output row once (k_den_emit); k_den_compute then overwrites the
+// output-row -> source-row map) and one launch of the row mover (gsr_rows.hip) writes every output row once; k_den_compute then overwrites the
 // few computed columns (children's xyz and scaling, PGSR clones' xyz).
 //
 // This unit is built with -ffp-contract=off: the selections are comparisons of float32 quotients and must not depend on FMA contraction.
 #include "gsr_common.h"
+#include <vector>
 
 #define DEN_BLOCK 1024
 #define DEN_NQ 6                    // scanned flags, in status order: clone, split, original kept, clone kept, children kept, split by the gradient rule
@@ -18,17 +19,6 @@
 #define DEN_F_KEEP_S 16u
 #define DEN_F_SPLIT_G 32u
 #define DEN_CNT 16                  // words of device counters
-
-__device__ __forceinline__ uint32_t den_wave_incl_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if ((int)lane >= d) v += t;
-    }
-    return v;
-}
 
 // classification of original i (see include/gsrast.h)
 __device__ __forceinline__ uint32_t den_classify(const gsr_densify_args& A, uint32_t i)
@@ -106,32 +96,6 @@ __global__ void __launch_bounds__(DEN_BLOCK) k_den_count(gsr_densify_args A, uin
     }
 }
 
-// block q scans the n block sums of flag q in place (exclusive); the total goes to counters[q] and status[q]
-__global__ void __launch_bounds__(DEN_BLOCK) k_den_scan_sums(uint32_t* __restrict__ sums_all, uint32_t n, uint32_t stride, uint32_t* __restrict__ counters,
-                                                             uint32_t* __restrict__ status)
-{
-    __shared__ uint32_t lds[17];
-    uint32_t* sums = sums_all + (size_t)blockIdx.x * stride;
-    const uint32_t chunk = (n + DEN_BLOCK - 1) / DEN_BLOCK;
-    const uint32_t b = min(n, threadIdx.x * chunk), e = min(n, b + chunk);
-    uint32_t sum = 0;
-    for (uint32_t i = b; i < e; i++) sum += sums[i];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t s = den_wave_incl_scan(sum);
-    if (lane == 63) lds[wave] = s;
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t w = (lane < DEN_BLOCK / 64) ? lds[lane] : 0;
-        const uint32_t ws = den_wave_incl_scan(w);
-        if (lane < DEN_BLOCK / 64) lds[lane] = ws - w;
-        if (lane == DEN_BLOCK / 64 - 1) lds[16] = ws;
-    }
-    __syncthreads();
-    uint32_t run = s - sum + lds[wave];
-    for (uint32_t i = b; i < e; i++) { const uint32_t v = sums[i]; sums[i] = run; run += v; }
-    if (threadIdx.x == 0) { counters[blockIdx.x] = lds[16]; status[blockIdx.x] = lds[16]; }
-}
-
 // rank[i]: position of i among the clones (a clone) or among the splits (a split parent); map: output row -> source row.
 // map has P * max(2, N) words: an original yields itself and a clone, or N children, never more.
 __global__ void __launch_bounds__(DEN_BLOCK) k_den_place(uint32_t P, uint32_t N, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums, uint32_t stride,
@@ -153,58 +117,7 @@ __global__ void __launch_bounds__(DEN_BLOCK) k_den_place(uint32_t P, uint32_t N,
         for (uint32_t r = 0; r < N; r++) map[(size_t)nO + nC + (size_t)r * nS + rank[4]] = i;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- emit
-#define DEN_MAX_T 24
-#define DEN_CHUNK 2048              // copy units per block of 256 threads
-struct DenEntry { const char* src; char* dst; uint64_t units; uint32_t upr, ulog, first_block, zero_new; };     // upr: units per row
-struct DenTable { int32_t count; uint32_t P, nO; uint32_t pad_; DenEntry e[DEN_MAX_T]; };
-
-// A lane owns one unit of consecutive output bytes: whole lines are written, reads are contiguous over every run of surviving rows.
-template <typename T>
-__device__ __forceinline__ void den_copy(const DenEntry& E, uint64_t base, const uint32_t* __restrict__ map, uint32_t P, uint32_t nO)
-{
-    const T* src = reinterpret_cast<const T*>(E.src);
-    T* dst = reinterpret_cast<T*>(E.dst);
-    const uint64_t end = min(E.units, base + DEN_CHUNK);
-    const uint64_t row0 = base / E.upr;
-    const uint32_t rem = (uint32_t)(base - row0 * E.upr);
-    T zero;
-    memset(&zero, 0, sizeof(T));
-    constexpr int IT = DEN_CHUNK / 256;
-    // three passes over the lane's IT units, so that the IT map reads, then the IT row reads, are in flight together
-    uint32_t srow[IT], col[IT];
-    T v[IT];
-#pragma unroll
-    for (int j = 0; j < IT; j++) {
-        const uint32_t k = threadIdx.x + j * 256, o = rem + k, dr = o / E.upr;
-        const uint64_t row = row0 + dr;
-        col[j] = o - dr * E.upr;
-        srow[j] = (base + k < end && !(E.zero_new && row >= nO)) ? map[row] : 0xFFFFFFFFu;
-    }
-#pragma unroll
-    for (int j = 0; j < IT; j++) {
-        v[j] = zero;
-        if (srow[j] < P) v[j] = src[(uint64_t)srow[j] * E.upr + col[j]];
-    }
-#pragma unroll
-    for (int j = 0; j < IT; j++) {
-        const uint32_t k = threadIdx.x + j * 256;
-        if (base + k < end) dst[base + k] = v[j];
-    }
-}
-
-__global__ void __launch_bounds__(256) k_den_emit(DenTable T, const uint32_t* __restrict__ map)
-{
-    int k = 0;
-#pragma unroll 1
-    for (int i = 1; i < T.count; i++) k = (blockIdx.x >= T.e[i].first_block) ? i : k;
-    const DenEntry& E = T.e[k];
-    const uint64_t base = (uint64_t)(blockIdx.x - E.first_block) * DEN_CHUNK;
-    if (E.ulog == 4) den_copy<uint4>(E, base, map, T.P, T.nO);
-    else if (E.ulog == 3) den_copy<uint2>(E, base, map, T.P, T.nO);
-    else den_copy<uint32_t>(E, base, map, T.P, T.nO);
-}
-
+// ---------------------------------------------------------------------------------------------------------------- computed columns
 // build_rotation (gssr/utils/general_utils.py:78-99) of the raw quaternion, times (z * s), plus the parent's position
 __device__ __forceinline__ void den_sample(const float* __restrict__ q4, const float* __restrict__ s, int cols, const float* __restrict__ z, const float* __restrict__ p,
                                            float* __restrict__ out)
@@ -286,7 +199,7 @@ extern "C" int gsr_densify_plan(const gsr_densify_args* a, void* scratch, size_t
     if (gsr_memset_async(status_dev, 0, 8 * 4, s) || gsr_memset_async(d.counters, 0, DEN_CNT * 4, s)) { gsr_set_error("densify_plan: counters"); return 1; }
     if (a->P) {
         hipLaunchKernelGGL(k_den_count, dim3(d.nblk), dim3(DEN_BLOCK), 0, s, *a, d.flags, d.sums, d.stride);
-        hipLaunchKernelGGL(k_den_scan_sums, dim3(DEN_NQ), dim3(DEN_BLOCK), 0, s, d.sums, d.nblk, d.stride, d.counters, status_dev);
+        gsr_scan_small(d.sums, d.nblk, DEN_NQ, d.stride, d.counters, status_dev, s);      // flag q's total to counters[q] and status[q]
         hipLaunchKernelGGL(k_den_place, dim3(d.nblk), dim3(DEN_BLOCK), 0, s, (uint32_t)a->P, (uint32_t)a->N, d.flags, d.sums, d.stride, d.counters, d.rank, d.map);
     }
     return gsr_check_launch("densify_plan", s, false);
@@ -299,36 +212,16 @@ extern "C" int gsr_densify_emit(const gsr_densify_args* a, const void* scratch, 
     if (!counts) { gsr_set_error("densify_emit: counts is NULL"); return 1; }
     const DenScratch d = den_carve((uint32_t)a->P, (uint32_t)a->N, const_cast<void*>(scratch));
     if (!scratch || d.bytes > scratch_bytes) { gsr_set_error("densify_emit: scratch too small: %zu < %zu", scratch_bytes, d.bytes); return 1; }
-    if (count < 0 || (count > 0 && !t)) { gsr_set_error("densify_emit: bad table"); return 1; }
     const uint32_t P = (uint32_t)a->P, N = (uint32_t)a->N;
     const uint32_t C = counts[0], S = counts[1], nO = counts[2], nC = counts[3], nS = counts[4];
     if (C > P || S > P - C || nO > P - S || nC > C || nS > S) { gsr_set_error("densify_emit: counts are not those of a plan over P=%u rows", P); return 1; }
     const uint64_t rows = (uint64_t)nO + nC + (uint64_t)N * nS;              // <= P * max(2, N) < 2^31: inside the map
     if (rows == 0) return 0;
-    for (int32_t i = 0; i < count; i++) {
-        if (t[i].row_bytes <= 0 || (t[i].row_bytes & 3)) { gsr_set_error("densify_emit: tensor %d: row_bytes must be a positive multiple of 4", i); return 1; }
-        if (!t[i].dst || !t[i].src) { gsr_set_error("densify_emit: tensor %d: null pointer", i); return 1; }
-        if (((uintptr_t)t[i].src | (uintptr_t)t[i].dst) & 3) { gsr_set_error("densify_emit: tensor %d: pointers must be 4-byte aligned", i); return 1; }
-    }
     hipStream_t s = (hipStream_t)stream;
-    int32_t i = 0;
-    while (i < count) {
-        DenTable T; T.count = 0; T.P = P; T.nO = nO; T.pad_ = 0;
-        uint64_t blocks = 0;
-        for (; i < count && T.count < DEN_MAX_T; i++) {
-            const uintptr_t al = (uintptr_t)t[i].src | (uintptr_t)t[i].dst | (uintptr_t)t[i].row_bytes;
-            const uint32_t ulog = (al & 15) == 0 ? 4u : ((al & 7) == 0 ? 3u : 2u);
-            DenEntry& E = T.e[T.count];
-            E.src = (const char*)t[i].src; E.dst = (char*)t[i].dst; E.ulog = ulog; E.upr = (uint32_t)(t[i].row_bytes >> ulog); E.zero_new = t[i].zero_new ? 1u : 0u;
-            if ((uint64_t)E.upr * DEN_CHUNK >= (1ull << 31)) { gsr_set_error("densify_emit: tensor %d: row_bytes too large", i); return 1; }
-            E.units = rows * E.upr;
-            E.first_block = (uint32_t)blocks;
-            blocks += (E.units + DEN_CHUNK - 1) / DEN_CHUNK;
-            if (blocks >= (1ull << 31)) { gsr_set_error("densify_emit: tensor %d: too many bytes for one launch", i); return 1; }
-            T.count++;
-        }
-        if (blocks) hipLaunchKernelGGL(k_den_emit, dim3((uint32_t)blocks), dim3(256), 0, s, T, d.map);
-    }
+    std::vector<gsr_rows_item> items;
+    for (int32_t i = 0; t && i < count; i++) items.push_back({t[i].src, t[i].dst, nullptr, t[i].row_bytes, 0, t[i].zero_new != 0});
+    const gsr_rows_map m = {d.map, nullptr, (uint32_t)rows, nO, P};                          // no tails: every output row comes through the map
+    if (gsr_rows_move("densify_emit", m, count, t ? items.data() : nullptr, true, s)) return 1;
     if (c) {
         const uint32_t n_clone_rows = c->noise_clone ? nC : 0u;
         const uint64_t total = (uint64_t)n_clone_rows + (uint64_t)N * nS;

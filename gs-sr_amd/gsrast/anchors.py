@@ -13,68 +13,11 @@ import math
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import check, ptr, stream_ptr
+from ._rows import Level, RowsTensor, _bytes, _f32, _lib, groups, install_, moments
 
-_vp = C.c_void_p
 PARAM_ATTRS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
 _SKIP = ("mlp", "conv", "feat_base", "embedding")        # param groups the reference's optimizer surgery leaves alone
-
-
-class Level(C.Structure):                 # include/gsrast.h gsr_anchor_level
-    _fields_ = [("Na", C.c_int32), ("N0", C.c_int32), ("k", C.c_int32), ("F", C.c_int32), ("scaling_stride", C.c_int32),
-                ("thr_lo", C.c_float), ("thr_hi", C.c_float), ("rand_thr", C.c_float), ("cell", C.c_float), ("origin", C.c_float * 3),
-                ("anchor", _vp), ("mask", _vp), ("offset", _vp), ("scaling", _vp), ("anchor_feat", _vp), ("grads", _vp), ("offset_mask", _vp), ("rand", _vp)]
-
-
-class RowsTensor(C.Structure):            # include/gsrast.h gsr_rows_tensor
-    _fields_ = [("src", _vp), ("dst", _vp), ("tail", _vp), ("row_bytes", C.c_int64), ("n_tail", C.c_int64)]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        sz = C.c_size_t
-        L.gsr_anchor_level_scratch_bytes.restype = sz; L.gsr_anchor_level_scratch_bytes.argtypes = [C.c_int32] * 3
-        L.gsr_anchor_level_find.restype = C.c_int
-        L.gsr_anchor_level_find.argtypes = [C.POINTER(Level), _vp, sz, _vp, _vp]
-        L.gsr_anchor_level_emit.restype = C.c_int
-        L.gsr_anchor_level_emit.argtypes = [C.POINTER(Level), _vp, sz, C.c_uint32, _vp, _vp, _vp]
-        L.gsr_rows_compact_scratch_bytes.restype = sz; L.gsr_rows_compact_scratch_bytes.argtypes = [C.c_int64]
-        L.gsr_rows_compact_multi.restype = C.c_int
-        L.gsr_rows_compact_multi.argtypes = [C.c_int64, _vp, C.c_int32, C.POINTER(RowsTensor), _vp, sz, _vp]
-        _bound = True
-    return L
-
-
-def _f32(t, name, shape=None):
-    """A contiguous float32 HIP tensor, or a RuntimeError that names the argument."""
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: expected scalar type Float but found {t.dtype}")
-    if shape is not None and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
-        raise RuntimeError(f"{name}: expected shape {list(shape)} but found {list(t.shape)}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    return t.detach().contiguous()
-
-
-def _bytes(t, name, n, like):
-    """bool / uint8 mask of n entries on the device of `like`, as bytes."""
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if not t.is_cuda or t.device != like.device:
-        raise RuntimeError(f"{name} must be a CUDA tensor on the device of the other arguments")
-    if t.dtype not in (torch.bool, torch.uint8):
-        raise RuntimeError(f"{name}: expected a bool or uint8 mask but found {t.dtype}")
-    if t.numel() != n:
-        raise RuntimeError(f"{name}: expected {n} entries but found {t.numel()}")
-    t = t.detach().contiguous().reshape(-1)
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
 def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell, thr_lo, thr_hi=math.inf, rand=None, rand_thr=0.0, mask=None,
@@ -259,19 +202,7 @@ def adjust_anchor_(model, check_interval=100, success_threshold=0.8, grad_thresh
         _f32(getattr(model, name), "model." + name, shp)
     scaling = model.get_scaling() if callable(model.get_scaling) else model.get_scaling
     scaling = _f32(scaling, "model.get_scaling", (N0, None))
-    groups = {}
-    for g in model.optimizer.param_groups:
-        gname = g.get("name", "")
-        if any(s in gname for s in _SKIP):
-            continue
-        if gname not in PARAM_ATTRS or len(g["params"]) != 1:
-            raise RuntimeError(f"model.optimizer: param group '{gname}' is not one of {sorted(PARAM_ATTRS)} with a single tensor")
-        if g["params"][0] is not getattr(model, PARAM_ATTRS[gname]):
-            raise RuntimeError(f"model.optimizer: param group '{gname}' does not hold model.{PARAM_ATTRS[gname]}")
-        groups[gname] = g
-    missing = sorted(set(PARAM_ATTRS) - set(groups))
-    if missing:
-        raise RuntimeError(f"model.optimizer: no param group named {missing}")
+    grp = groups(model, PARAM_ATTRS, _SKIP)
 
     # 1. statistics -> per-slot gradient and the slots that were seen often enough
     grads = model.offset_gradient_accum / model.offset_denom
@@ -292,46 +223,22 @@ def adjust_anchor_(model, check_interval=100, success_threshold=0.8, grad_thresh
     model.anchor_demon.masked_fill_(anchors_mask, 0.0)
     keep = ~prune.reshape(-1)
     # 6. one compaction + append pass: [old[keep] ; new]
-    names = list(groups)
-    tensors, tails, slots = [], [], []
-    for n in names:
-        p = groups[n]["params"][0]
-        tensors.append(p); tails.append(d[n]); slots.append(("param", n))
-        st = model.optimizer.state.get(p, None)
-        if st is not None and "exp_avg" in st:
-            for key in ("exp_avg", "exp_avg_sq"):
-                tensors.append(st[key]); tails.append(U); slots.append((key, n))
-    for n in ("opacity_accum", "anchor_demon"):
-        tensors.append(getattr(model, n)); tails.append(U); slots.append(("attr", n))
-    for n in ("offset_gradient_accum", "offset_denom"):
-        tensors.append(getattr(model, n).reshape(N0, k)); tails.append(U); slots.append(("attr_k", n))
-    outs = rows_compact(keep, tensors, tails)
+    tensors, tails, carried = [], [], {}
+    for n, g in grp.items():
+        p = g["params"][0]
+        carried[n] = moments(model.optimizer, p)
+        tensors += [p] + list(carried[n] or ()); tails += [d[n]] + [U] * (2 if carried[n] else 0)
+    accs = ("opacity_accum", "anchor_demon", "offset_gradient_accum", "offset_denom")
+    tensors += [getattr(model, n) for n in accs[:2]] + [getattr(model, n).reshape(N0, k) for n in accs[2:]]
+    outs = iter(rows_compact(keep, tensors, tails + [U] * 4))
     # 7. fresh parameters, carried optimizer state
-    new_state = {n: {} for n in names}
-    for (kind, n), out in zip(slots, outs):
-        if kind == "param":
-            new_state[n]["param"] = out
-        elif kind in ("exp_avg", "exp_avg_sq"):
-            new_state[n][kind] = out
-        elif kind == "attr":
-            setattr(model, n, out)
-        else:
-            setattr(model, n, out.reshape(-1, 1))
-    for n in names:
-        g = groups[n]
-        old = g["params"][0]
-        data = new_state[n]["param"]
+    for n, g in grp.items():
+        data = next(outs)
         if n == "scaling":
             data[:, 3:].clamp_(max=0.05)                         # 8. scaffold_gaussian.py:527-531, on the raw parameter
-        new = torch.nn.Parameter(data.requires_grad_(True))
-        st = model.optimizer.state.get(old, None)
-        if st is not None:
-            if "exp_avg" in st:
-                st["exp_avg"] = new_state[n]["exp_avg"]; st["exp_avg_sq"] = new_state[n]["exp_avg_sq"]
-            del model.optimizer.state[old]
-            model.optimizer.state[new] = st
-        g["params"][0] = new
-        setattr(model, PARAM_ATTRS[n], new)
+        install_(model, g, PARAM_ATTRS[n], data, (next(outs), next(outs)) if carried[n] else None)
+    for n in accs:
+        setattr(model, n, next(outs).reshape(-1, 1))
     # 9.
     Na = model._anchor.shape[0]
     model.max_radii2D = torch.zeros(Na, dtype=torch.float32, device=dev)

@@ -12,59 +12,18 @@ prunes anything; max_screen_size only switches the world-size test on.  DESIGN.m
 
 There is no CPU fallback: host tensors raise."""
 import ctypes as C
+import functools
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import check, ptr, stream_ptr
+from ._rows import Args, Compute, Tensor, _lib, groups, install_
+from ._rows import _f32 as _rows_f32, moments as _moments
 
-_vp = C.c_void_p
+_f32 = functools.partial(_rows_f32, wild="*")                # a free dimension prints as '*'
+
 GROUPS = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
 SIZE_PRUNE, CLONE_CAP, SPLIT_CAP, ABS_CAP = 1, 2, 4, 8
-
-
-class Args(C.Structure):                  # include/gsrast.h gsr_densify_args
-    _fields_ = [("P", C.c_int32), ("scaling_cols", C.c_int32), ("N", C.c_int32), ("flags", C.c_int32)] + \
-               [(n, C.c_float) for n in ("clone_thr", "split_thr", "abs_thr", "dense_thr", "min_opacity", "world_thr", "abs_radii_thr", "child_div",
-                                         "clone_cap", "split_cap", "abs_cap")] + \
-               [(n, _vp) for n in ("accum", "denom", "accum_abs", "denom_abs", "scaling", "opacity", "max_radii2D", "masked_out")]
-
-
-class Tensor(C.Structure):                # include/gsrast.h gsr_densify_tensor
-    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", C.c_int64), ("zero_new", C.c_int32), ("pad_", C.c_int32)]
-
-
-class Compute(C.Structure):               # include/gsrast.h gsr_densify_compute
-    _fields_ = [(n, _vp) for n in ("xyz", "rotation", "xyz_dst", "scaling_dst", "noise_split", "noise_clone")]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        sz = C.c_size_t
-        L.gsr_densify_plan_scratch_bytes.restype = sz; L.gsr_densify_plan_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-        L.gsr_densify_plan.restype = C.c_int
-        L.gsr_densify_plan.argtypes = [C.POINTER(Args), _vp, sz, _vp, _vp]
-        L.gsr_densify_emit.restype = C.c_int
-        L.gsr_densify_emit.argtypes = [C.POINTER(Args), _vp, sz, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(Tensor), C.POINTER(Compute), _vp]
-        _bound = True
-    return L
-
-
-def _f32(t, name, shape=None, device_check=True):
-    """A contiguous float32 HIP tensor, or a RuntimeError that names the argument."""
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: expected scalar type Float but found {t.dtype}")
-    if shape is not None and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
-        raise RuntimeError(f"{name}: expected shape {[('*' if s is None else s) for s in shape]} but found {list(t.shape)}")
-    if device_check and not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    return t.detach().contiguous()
 
 
 def _noise(t, name, N):
@@ -238,38 +197,9 @@ def clone_split_prune(params, moments, xyz_gradient_accum, denom, scaling_act, o
     return out_p, out_m, {"clones": n_clone, "splits": n_split, "pruned": P + n_clone + (N - 1) * n_split - rows, "rows": rows}
 
 
-def _groups(model):
-    groups = {}
-    for g in model.optimizer.param_groups:
-        name = g.get("name", "")
-        if name not in GROUPS:
-            raise RuntimeError(f"model.optimizer: unknown group name '{name}', expected one of {sorted(GROUPS)}")
-        if len(g["params"]) != 1 or g["params"][0] is not getattr(model, GROUPS[name]):
-            raise RuntimeError(f"model.optimizer: param group '{name}' must hold model.{GROUPS[name]} alone")
-        groups[name] = g
-    missing = sorted(set(GROUPS) - set(groups))
-    if missing:
-        raise RuntimeError(f"model.optimizer: no param group named {missing}")
-    return groups
-
-
 def _get(model, name):
     v = getattr(model, name)
     return v() if callable(v) and not isinstance(v, torch.Tensor) else v
-
-
-def _install(model, group, name, data, moments=None):
-    """A fresh leaf Parameter in the place of the group's tensor; the Adam state moves to it (`step` untouched)."""
-    old = group["params"][0]
-    new = torch.nn.Parameter(data.requires_grad_(True))
-    st = model.optimizer.state.get(old, None)
-    if st is not None:
-        if moments is not None and "exp_avg" in st:
-            st["exp_avg"], st["exp_avg_sq"] = moments
-        del model.optimizer.state[old]
-        model.optimizer.state[new] = st
-    group["params"][0] = new
-    setattr(model, GROUPS[name], new)
 
 
 @torch.no_grad()
@@ -284,13 +214,9 @@ def densify_and_prune_(model, max_grad, min_opacity, extent, max_screen_size, ab
     for name in need:
         if not hasattr(model, name):
             raise RuntimeError(f"model: attribute {name} is missing")
-    groups = _groups(model)
-    params = {n: g["params"][0] for n, g in groups.items()}
-    moments = {}
-    for n, g in groups.items():
-        st = model.optimizer.state.get(g["params"][0], None)
-        if st is not None and "exp_avg" in st:
-            moments[n] = (st["exp_avg"], st["exp_avg_sq"])
+    grp = groups(model, GROUPS)
+    params = {n: g["params"][0] for n, g in grp.items()}
+    moments = {n: m for n, m in ((n, _moments(model.optimizer, p)) for n, p in params.items()) if m is not None}
     kw = {}
     if pgsr:
         kw = dict(xyz_gradient_accum_abs=model.xyz_gradient_accum_abs, denom_abs=model.denom_abs, abs_max_grad=abs_max_grad,
@@ -299,8 +225,8 @@ def densify_and_prune_(model, max_grad, min_opacity, extent, max_screen_size, ab
     out_p, out_m, counts = clone_split_prune(params, moments, model.xyz_gradient_accum, model.denom, _get(model, "get_scaling"), _get(model, "get_opacity"),
                                              model.max_radii2D, max_grad=max_grad, min_opacity=min_opacity, extent=extent, percent_dense=model.percent_dense,
                                              max_screen_size=max_screen_size, N=N, noise_split=noise_split, noise_clone=noise_clone, generator=generator, **kw)
-    for n, g in groups.items():
-        _install(model, g, n, out_p[n], out_m.get(n))
+    for n, g in grp.items():
+        install_(model, g, GROUPS[n], out_p[n], out_m.get(n))
     rows = counts["rows"]
     dev = out_p["xyz"].device
     z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
@@ -324,7 +250,7 @@ def reset_opacity_(model):
         if g.get("name", "") == "opacity":
             if g["params"][0] is not model._opacity:
                 raise RuntimeError("model.optimizer: param group 'opacity' must hold model._opacity alone")
-            _install(model, g, "opacity", new, (torch.zeros_like(new), torch.zeros_like(new)))
+            install_(model, g, "_opacity", new, (torch.zeros_like(new), torch.zeros_like(new)))
             return
     raise RuntimeError("model.optimizer: no param group named ['opacity']")
 

@@ -7,9 +7,8 @@ appended with one cat per tensor, the children with another, the split parents a
 tensor, over 6 parameters and 12 Adam moments.  It is the baseline; the code under test never is.  Inputs: tests/densify_cases.make_inputs at SH
 degree 3 (15 rest coefficients), about 10 % cloned, 10 % split, 5 % pruned.  Times are HIP-event times of one whole call (host synchronisations
 included), clocks warmed, each path warmed once on the same shape; launches and per-kernel device times come from the torch profiler, host
-synchronisations from torch's sync debug mode, peak memory from the caching allocator's statistics, each in a run of its own.  The copy kernel's
-algorithmic rate (bytes it must read and write / its device time) is set beside that of gsr_rows_compact_multi's copy kernel on the same tensors
-with the same number of surviving rows.  Prints and writes JSON."""
+synchronisations from torch's sync debug mode, peak memory from the caching allocator's statistics, each in a run of its own.  The copy kernel
+(the row mover, k_rows_move) is reported with its algorithmic rate: the bytes it must read and write over its device time.  Prints and writes JSON."""
 import argparse
 import json
 import os
@@ -23,7 +22,7 @@ import numpy as np      # noqa: E402
 import torch            # noqa: E402
 import densify_cases as DC          # noqa: E402
 import ref_densify_torch as R       # noqa: E402
-from gsrast import anchors, densify   # noqa: E402
+from gsrast import densify   # noqa: E402
 
 HBM = 8.0e12
 RULES = dict(DC.RULES, max_screen_size=20)
@@ -151,7 +150,7 @@ def main():
             try:
                 ent["kernel_launches"], per = profile_kernels(fn, b)
                 if tag == "hip":
-                    ent["kernel_us"] = {k: round(v, 1) for k, v in per.items() if "k_den_" in k}
+                    ent["kernel_us"] = {k: round(v, 1) for k, v in per.items() if "k_den_" in k or "k_rows_move" in k}
             except Exception as e:                                # the profiler is optional equipment
                 ent["kernel_launches"] = f"not measured ({type(e).__name__})"
             try:
@@ -170,32 +169,20 @@ def main():
             del m
             row[tag] = ent
             print(json.dumps({"P": P, tag: ent}), flush=True)
-        # the copy kernel against gsr_rows_compact_multi's on the same tensors (a prune of as many rows as the call carried over)
-        try:
-            m = build("gsrast")
-            s_act, o_act = m.get_scaling.detach(), m.get_opacity.detach()
-            clone, split, prune_self, _ = R.classify(m.xyz_gradient_accum, m.denom, s_act, o_act, m.max_radii2D, **RULES)
-            keep = ~split & ~prune_self
-            n_o = int(keep.sum())
-            tensors = list(m.tensors().values()) + [t for pair in m.moments().values() for t in pair]
-            anchors.rows_compact(keep, tensors)                                       # warm
-            _, per = profile_kernels(lambda mm: anchors.rows_compact(keep, tensors), lambda: m)
-            us_rows = sum(v for k, v in per.items() if "k_rows_compact" in k)
-            rb = row["hip"]["row_bytes_params"]
-            rows = row["hip"]["rows_after"]
-            bytes_rows = 3 * rb * (n_o + n_o)                                         # 18 tensors: read the kept rows, write them
-            bytes_emit = rb * (rows + rows) + 2 * rb * (n_o + rows)                   # parameters: read + write every output row; moments: read carried rows, write all
-            us_emit = sum(v for k, v in row["hip"].get("kernel_us", {}).items() if "k_den_emit" in k)
-            cmp_ = {"rows_carried": n_o, "rows_compact_us": round(us_rows, 1), "rows_compact_bytes": bytes_rows, "emit_us": round(us_emit, 1), "emit_bytes": bytes_emit}
-            if us_rows > 0 and us_emit > 0:
-                cmp_["rows_compact_TBps"] = round(bytes_rows / us_rows / 1e6, 3); cmp_["emit_TBps"] = round(bytes_emit / us_emit / 1e6, 3)
-                cmp_["emit_hbm_fraction"] = round(bytes_emit / (us_emit * 1e-6) / HBM, 3)
-                cmp_["emit_over_rows_compact"] = round(cmp_["emit_TBps"] / cmp_["rows_compact_TBps"], 2)
-            cmp_["call_hbm_fraction"] = round(bytes_emit / (row["hip"]["ms_median"] * 1e-3) / HBM, 3)
-            row["copy_kernel"] = cmp_
-            del m, tensors
-        except Exception as e:
-            row["copy_kernel"] = f"not measured ({type(e).__name__}: {e})"
+        # the copy kernel's algorithmic bytes -- parameters: read + write every output row; moments: read the carried rows, write all
+        m = build("gsrast")
+        _, split, prune_self, _ = R.classify(m.xyz_gradient_accum, m.denom, m.get_scaling.detach(), m.get_opacity.detach(), m.max_radii2D, **RULES)
+        n_o = int((~split & ~prune_self).sum())
+        del m
+        rb, rows = row["hip"]["row_bytes_params"], row["hip"]["rows_after"]
+        bytes_emit = rb * (rows + rows) + 2 * rb * (n_o + rows)
+        us_emit = sum(v for k, v in row["hip"].get("kernel_us", {}).items() if "k_rows_move" in k)
+        cmp_ = {"rows_carried": n_o, "emit_us": round(us_emit, 1), "emit_bytes": bytes_emit}
+        if us_emit > 0:
+            cmp_["emit_TBps"] = round(bytes_emit / us_emit / 1e6, 3)
+            cmp_["emit_hbm_fraction"] = round(bytes_emit / (us_emit * 1e-6) / HBM, 3)
+        cmp_["call_hbm_fraction"] = round(bytes_emit / (row["hip"]["ms_median"] * 1e-3) / HBM, 3)
+        row["copy_kernel"] = cmp_
         row["speedup"] = round(row["torch_chain"]["ms_median"] / row["hip"]["ms_median"], 2)
         row["not_slower_than_chain"] = bool(row["hip"]["ms_median"] <= row["torch_chain"]["ms_median"])
         print(json.dumps({"P": P, "copy_kernel": row["copy_kernel"], "speedup": row["speedup"]}), flush=True)
