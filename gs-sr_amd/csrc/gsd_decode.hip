@@ -15,6 +15,8 @@
 //   * layer-1 weights are first repacked (k_pack) to a fixed [head][32][48] layout: columns feat 0..31, view 32..34, dist 35, level 36,
 //     effective bias 37 (b1 + W1[:, appearance cols] . appearance) -- absent inputs get zero weights, so the hot kernels carry no flags.
 #include "gsr_common.h"
+#include "gsr_reduce.h"
+#include "gsr_scan.h"
 #include "../../include/gsdecode.h"
 
 #define GSD_XC 37            // x = [feat 32, view 3, dist, level]
@@ -48,17 +50,6 @@ struct DecArgs {
 __device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------ scan (exclusive, in place)
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
 // Exclusive scan of data[0, n) in place, one launch, no ticket: every workgroup scans its 1024 words, PUBLISHES its total (flag word = ready bit |
 // total) and then adds up the published totals of all workgroups in front of it -- one load per predecessor, spinning on the ready bits.  Workgroups
 // are dispatched in index order and only ever wait for lower indices, so the wait ends; nobody waits in a chain (each total is published before its
@@ -76,7 +67,7 @@ __global__ void __launch_bounds__(1024) k_scan_lookback(uint32_t* __restrict__ d
     __shared__ uint32_t s_prev;
     const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
     const uint32_t v = i < n ? data[i] : 0u;
-    const uint32_t incl = wave_scan_incl(v);
+    const uint32_t incl = wave_incl_scan(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
@@ -1107,35 +1098,10 @@ __global__ void __launch_bounds__(ST_BLOCK) k_stats_count(int Nv, int k, const u
 {
     __shared__ uint32_t ws[ST_BLOCK / 64];
     const int v = blockIdx.x * ST_BLOCK + threadIdx.x;
-    uint32_t c = v < Nv ? st_count(mask, v, k) : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    const uint32_t c = wave_sum(v < Nv ? st_count(mask, v, k) : 0u);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) blocksum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-__global__ void __launch_bounds__(1024) k_stats_scan(uint32_t* __restrict__ blocksum, uint32_t nblk)
-{
-    __shared__ uint32_t wa[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nblk; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nblk ? blocksum[i] : 0u;
-        uint32_t a = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(a, d, 64); if ((threadIdx.x & 63) >= d) a += o; }
-        if ((threadIdx.x & 63) == 63) wa[threadIdx.x >> 6] = a;
-        __syncthreads();
-        uint32_t off = carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += wa[w];
-        if (i < nblk) blocksum[i] = off + a - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = off + a;
-        __syncthreads();
-    }
 }
 
 __global__ void __launch_bounds__(ST_BLOCK) k_stats_apply(int Nv, int k, const int32_t* __restrict__ vis_idx, const float* __restrict__ nop,
@@ -1143,16 +1109,10 @@ __global__ void __launch_bounds__(ST_BLOCK) k_stats_apply(int Nv, int k, const i
                                                           int gs, const uint32_t* __restrict__ blockoff, float* __restrict__ opacity_accum,
                                                           float* __restrict__ anchor_demon, float* __restrict__ off_grad, float* __restrict__ off_den)
 {
-    __shared__ uint32_t ws[ST_BLOCK / 64];
+    __shared__ uint32_t lds[17];
     const int v = blockIdx.x * ST_BLOCK + threadIdx.x;
-    const uint32_t c = v < Nv ? st_count(mask, v, k) : 0u;
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if ((threadIdx.x & 63) >= d) inc += o; }
-    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t p = blockoff[blockIdx.x] + inc - c;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) p += ws[w];
+    uint32_t all;
+    uint32_t p = blockoff[blockIdx.x] + block_excl_scan(v < Nv ? st_count(mask, v, k) : 0u, lds, &all);
     if (v >= Nv) return;
     const int a = vis_idx[v];
     if (a < 0) return;                                                // padding row (gsd_compact_visible_padded)
@@ -1187,7 +1147,7 @@ extern "C" int gsd_training_stats(int32_t Nv, int32_t k, const int32_t* vis_idx,
     const uint32_t nblk = ((uint32_t)Nv + ST_BLOCK - 1) / ST_BLOCK;
     uint32_t* bs = (uint32_t*)scratch;
     hipLaunchKernelGGL(k_stats_count, dim3(nblk), dim3(ST_BLOCK), 0, s, Nv, k, mask, bs);
-    hipLaunchKernelGGL(k_stats_scan, dim3(1), dim3(1024), 0, s, bs, nblk);
+    gsr_scan_small(bs, nblk, 1, 0, nullptr, nullptr, s);
     hipLaunchKernelGGL(k_stats_apply, dim3(nblk), dim3(ST_BLOCK), 0, s, Nv, k, vis_idx, neural_opacity, mask, update_filter, viewspace_grad,
                        grad_stride, (const uint32_t*)bs, opacity_accum, anchor_demon, offset_gradient_accum, offset_denom);
     return gsr_check_launch("training_stats", s, false);

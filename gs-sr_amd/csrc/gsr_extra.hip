@@ -3,6 +3,7 @@
 //   gsr_dist2          : simple_knn.distCUDA2 (mean squared distance to the 3 nearest neighbours)
 #include <algorithm>
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 // torch.nn.functional.grid_sample(mode='bilinear', padding_mode='border', align_corners=True), one sample.
 // Coordinates are clamped to [0, size-1]; corner weights as ATen: (x1 - x), (x - x0); out-of-range corners add 0.
@@ -240,11 +241,8 @@ __global__ void __launch_bounds__(256) k_loss_l1_linear(int64_t n4c, int64_t nc,
     for (int64_t i = 4 * n4a + t0; i < na; i += stride) acc += aux[i] * waux[i];
     // block reduction, one atomic per block
     __shared__ float red[4];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss_out, (red[0] + red[1]) + (red[2] + red[3]));
+    const float tot = block_sum256(acc, red);
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_out, tot);
 }
 
 extern "C" int gsr_loss_l1_linear(int64_t n_color, const float* color, const float* gt, float* dL_dcolor, int64_t n_aux, const float* aux,

@@ -12,6 +12,7 @@
 //                zero-padded correlation is the same correlation) + the L1 sign term.
 // Algorithmic bytes per pixel-channel: fwd 8 read + 12 written, bwd 12 + 8 read + 4 written = 44 B.
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #define SS_T 32                         // output tile width
 #ifndef SS_TY
@@ -36,15 +37,6 @@ __constant__ float c_win[11] = {1.028380124e-03f, 7.598758209e-03f, 3.600077331e
 #define SS_LOAD_TAPS(w)                                                          \
     float w[11];                                                                 \
     _Pragma("unroll") for (int i_ = 0; i_ < 11; i_++) { w[i_] = c_win[i_]; asm volatile("" : "+v"(w[i_])); }
-
-__device__ __forceinline__ float block_sum256(float v, float* red)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // 32x32 outputs per 256-thread block.  Horizontal pass: a work item = one patch row x 4 adjacent output columns (42 rows x 8 groups);
 // vertical pass: one output column x 4 adjacent output rows (32 x 8 = 256 items, one per thread).
@@ -142,7 +134,7 @@ __global__ void __launch_bounds__(256) k_ssim_fwd(int H, int W, const float* __r
     const float ts = block_sum256(ssim, red);
     __syncthreads();
     const float tl = block_sum256(l1, red);
-    // one partial per block, summed by k_ssim_finish: same-address atomics from thousands of blocks serialise (measured 0.5 ms)
+    // one partial per block, summed by k_finish2 (gsr_reduce.h)
     if (threadIdx.x == 0) partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = make_float2(tl, ts);
 }
 
@@ -229,29 +221,6 @@ __global__ void __launch_bounds__(256) k_ssim_bwd(int H, int W, const float* __r
     }
 }
 
-__global__ void __launch_bounds__(1024) k_ssim_finish(const float2* __restrict__ partial, int n, float* loss, float inv_n, float lambda)
-{
-    __shared__ float r1[16], r2[16];
-    float a = 0.f, b = 0.f;
-    for (int i0 = 0; i0 < n; i0 += 8 * 1024) {           // eight loads in flight per thread, summed in index order
-        float2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const int i = i0 + u * 1024 + threadIdx.x; v[u] = partial[i < n ? i : 0]; if (i >= n) v[u] = make_float2(0.f, 0.f); }
-#pragma unroll
-        for (int u = 0; u < 8; u++) { a += v[u].x; b += v[u].y; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = a; r2[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < 16; w++) { sa += r1[w]; sb += r2[w]; }
-        const float l1 = sa * inv_n, ss = sb * inv_n;
-        loss[0] = l1; loss[1] = ss; loss[2] = (1.0f - lambda) * l1 + lambda * (1.0f - ss);
-    }
-}
-
 static size_t ssim_blocks(int32_t C, int32_t H, int32_t W) { return (size_t)gsr_div_up(W, SS_T) * gsr_div_up(H, SS_TY) * C; }
 extern "C" size_t gsr_loss_l1_ssim_scratch_bytes(int32_t C, int32_t H, int32_t W)
 {
@@ -273,7 +242,7 @@ extern "C" int gsr_loss_l1_ssim(int32_t C, int32_t H, int32_t W, const float* im
     hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(256), 0, s, H, W, img, gt, (float*)scratch, plane_all, partial);
     hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(256), 0, s, H, W, img, gt, (const float*)scratch, plane_all, (1.0f - lambda_dssim) * inv_n,
                        lambda_dssim * inv_n, dL_dimg);
-    hipLaunchKernelGGL(k_ssim_finish, dim3(1), dim3(1024), 0, s, (const float2*)partial, (int)ssim_blocks(C, H, W), loss_out, inv_n, lambda_dssim);
+    gsr_finish2((const float2*)partial, (int)ssim_blocks(C, H, W), FinishSsim{loss_out, inv_n, lambda_dssim}, s);
     return gsr_check_launch("loss_l1_ssim", s, false);
 }
 
@@ -306,6 +275,42 @@ struct GeoArgs {
 
 __device__ __forceinline__ float nan0(float v) { return (isnan(v) || isinf(v)) ? 0.0f : v; }
 
+// [x y 1] @ ray_mat
+__device__ __forceinline__ void geo_ray(const float* rm, float fx, float fy, float* r)
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) r[c] = fx * rm[c] + fy * rm[3 + c] + rm[6 + c];
+}
+
+// depth_to_normal at (py, px) of the P tile: central differences dx (down - up) and dy (right - left), n = normalize(cross(dx, dy))
+__device__ __forceinline__ void geo_stencil(const float (&sP)[3][GEO_PY][GEO_PX + 1], int py, int px, float* dx, float* dy, float* n, float& len, float& inv)
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) { dx[c] = sP[c][py + 1][px] - sP[c][py - 1][px]; dy[c] = sP[c][py][px + 1] - sP[c][py][px - 1]; }
+    const float c0 = dx[1] * dy[2] - dx[2] * dy[1], c1 = dx[2] * dy[0] - dx[0] * dy[2], c2 = dx[0] * dy[1] - dx[1] * dy[0];
+    len = sqrtf(c0 * c0 + c1 * c1 + c2 * c2);
+    inv = 1.0f / fmaxf(len, 1e-12f);
+    n[0] = c0 * inv; n[1] = c1 * inv; n[2] = c2 * inv;
+}
+
+// its adjoint: dn = d loss / d n  ->  g = d loss / d (dx, dy)  (dn projected off n, then back through the cross product)
+__device__ __forceinline__ void geo_stencil_adjoint(const float* dn, const float* n, float len, float inv, const float* dx, const float* dy, float* g)
+{
+    float dc[3];
+    const float nd = len > 1e-12f ? n[0] * dn[0] + n[1] * dn[1] + n[2] * dn[2] : 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; c++) dc[c] = (dn[c] - n[c] * nd) * inv;
+    g[0] = dy[1] * dc[2] - dy[2] * dc[1]; g[1] = dy[2] * dc[0] - dy[0] * dc[2]; g[2] = dy[0] * dc[1] - dy[1] * dc[0];
+    g[3] = dc[1] * dx[2] - dc[2] * dx[1]; g[4] = dc[2] * dx[0] - dc[0] * dx[2]; g[5] = dc[0] * dx[1] - dc[1] * dx[0];
+}
+
+// d loss / d P at (qy, qx) of the g tile: every P is the +/- neighbour of four stencils
+__device__ __forceinline__ void geo_gather_dP(const float (&sG)[6][GEO_GY][GEO_GX + 1], int qy, int qx, float* dP)
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) dP[c] = sG[c][qy - 1][qx] - sG[c][qy + 1][qx] + sG[3 + c][qy][qx - 1] - sG[3 + c][qy][qx + 1];
+}
+
 __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
 {
     __shared__ float sP[3][GEO_PY][GEO_PX + 1];
@@ -332,13 +337,13 @@ __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
         for (int i = 0; i < GEO_NLD; i++) {
             const int e = threadIdx.x + i * 256, ly = e / GEO_PX, lx = e % GEO_PX, gy = y0 + ly - 2, gx = x0 + lx - 2;
             if (e < GEO_PX * GEO_PY) {
-                float P0 = 0.f, P1 = 0.f, P2 = 0.f;
+                float P[3] = {0.f, 0.f, 0.f};
                 if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
                     const float d = nan0(v0[i] / va[i]) * (1.0f - p.depth_ratio) + p.depth_ratio * nan0(v5[i]);
-                    const float fx = (float)gx, fy = (float)gy;
-                    P0 = d * (fx * rm[0] + fy * rm[3] + rm[6]); P1 = d * (fx * rm[1] + fy * rm[4] + rm[7]); P2 = d * (fx * rm[2] + fy * rm[5] + rm[8]);
+                    geo_ray(rm, (float)gx, (float)gy, P);
+                    P[0] *= d; P[1] *= d; P[2] *= d;
                 }
-                sP[0][ly][lx] = P0; sP[1][ly][lx] = P1; sP[2][ly][lx] = P2;
+                sP[0][ly][lx] = P[0]; sP[1][ly][lx] = P[1]; sP[2][ly][lx] = P[2];
             }
         }
     }
@@ -353,23 +358,12 @@ __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
             float nw[3];
 #pragma unroll
             for (int c = 0; c < 3; c++) nw[c] = nv0 * nr[c] + nv1 * nr[3 + c] + nv2 * nr[6 + c];
-            const int py = ly + 1, px = lx + 1;                 // position in the P tile
-            float dx[3], dy[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) { dx[c] = sP[c][py + 1][px] - sP[c][py - 1][px]; dy[c] = sP[c][py][px + 1] - sP[c][py][px - 1]; }
-            const float c0 = dx[1] * dy[2] - dx[2] * dy[1], c1 = dx[2] * dy[0] - dx[0] * dy[2], c2 = dx[0] * dy[1] - dx[1] * dy[0];
-            const float len = sqrtf(c0 * c0 + c1 * c1 + c2 * c2);
-            const float inv = 1.0f / fmaxf(len, 1e-12f);
-            n[0] = c0 * inv; n[1] = c1 * inv; n[2] = c2 * inv;
+            float dx[3], dy[3], dn[3], len, inv;
+            geo_stencil(sP, ly + 1, lx + 1, dx, dy, n, len, inv);       // (ly + 1, lx + 1): position in the P tile
             dot = a * (nw[0] * n[0] + nw[1] * n[1] + nw[2] * n[2]);
-            float dn[3], dc[3];
 #pragma unroll
             for (int c = 0; c < 3; c++) dn[c] = -p.wn * a * nw[c];
-            const float nd = len > 1e-12f ? n[0] * dn[0] + n[1] * dn[1] + n[2] * dn[2] : 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; c++) dc[c] = (dn[c] - n[c] * nd) * inv;
-            g[0] = dy[1] * dc[2] - dy[2] * dc[1]; g[1] = dy[2] * dc[0] - dy[0] * dc[2]; g[2] = dy[0] * dc[1] - dy[1] * dc[0];
-            g[3] = dc[1] * dx[2] - dc[2] * dx[1]; g[4] = dc[2] * dx[0] - dc[0] * dx[2]; g[5] = dc[0] * dx[1] - dc[1] * dx[0];
+            geo_stencil_adjoint(dn, n, len, inv, dx, dy, g);
             n[0] *= a; n[1] *= a; n[2] *= a;                   // surf_normal = n * alpha
         }
 #pragma unroll
@@ -384,11 +378,10 @@ __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
     if (gx < W && gy < H) {
         const size_t o = (size_t)gy * W + gx;
         const int qy = ly + 1, qx = lx + 1;                    // position in the g tile
-        float dP[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) dP[c] = sG[c][qy - 1][qx] - sG[c][qy + 1][qx] + sG[3 + c][qy][qx - 1] - sG[3 + c][qy][qx + 1];
-        const float fx = (float)gx, fy = (float)gy;
-        const float dd = dP[0] * (fx * rm[0] + fy * rm[3] + rm[6]) + dP[1] * (fx * rm[1] + fy * rm[4] + rm[7]) + dP[2] * (fx * rm[2] + fy * rm[5] + rm[8]);
+        float dP[3], r[3];
+        geo_gather_dP(sG, qy, qx, dP);
+        geo_ray(rm, (float)gx, (float)gy, r);
+        const float dd = dP[0] * r[0] + dP[1] * r[1] + dP[2] * r[2];
         const float a0 = p.allmap[o], a = p.allmap[N + o], m = p.allmap[5 * N + o], q = a0 / a;
         const bool okq = !(isnan(q) || isinf(q)), okm = !(isnan(m) || isinf(m));
         p.dL[o] = okq ? dd * (1.0f - p.depth_ratio) / a : 0.0f;
@@ -416,28 +409,6 @@ __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
     if (threadIdx.x == 0) p.partial[blockIdx.y * gridDim.x + blockIdx.x] = make_float2(te, td);
 }
 
-__global__ void __launch_bounds__(1024) k_geo_finish(const float2* __restrict__ partial, int n, float* loss, float inv_n, float ln, float ld)
-{
-    __shared__ float r1[16], r2[16];
-    float a = 0.f, b = 0.f;
-    for (int i0 = 0; i0 < n; i0 += 8 * 1024) {           // eight loads in flight per thread, summed in index order
-        float2 q[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const int i = i0 + u * 1024 + threadIdx.x; q[u] = partial[i < n ? i : 0]; if (i >= n) q[u] = make_float2(0.f, 0.f); }
-#pragma unroll
-        for (int u = 0; u < 8; u++) { a += q[u].x; b += q[u].y; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = a; r2[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < 16; w++) { sa += r1[w]; sb += r2[w]; }
-        loss[0] = sa * inv_n; loss[1] = sb * inv_n; loss[2] = ln * loss[0] + ld * loss[1];
-    }
-}
-
 extern "C" size_t gsr_loss_surfel_geo_scratch_bytes(int32_t H, int32_t W)
 {
     return (H > 0 && W > 0) ? (size_t)gsr_div_up(W, GEO_TX) * gsr_div_up(H, GEO_TY) * sizeof(float2) : 0;
@@ -459,8 +430,7 @@ extern "C" int gsr_loss_surfel_geo(int32_t H, int32_t W, const float* allmap, co
     a.o_depth = out_surf_depth; a.o_nw = out_normal_world; a.o_sn = out_surf_normal;
     const dim3 grid(gsr_div_up(W, GEO_TX), gsr_div_up(H, GEO_TY));
     hipLaunchKernelGGL(k_surfel_geo, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(1024), 0, s, (const float2*)scratch, (int)(grid.x * grid.y), loss_out, inv_n, lambda_normal,
-                       lambda_dist);
+    gsr_finish2((const float2*)scratch, (int)(grid.x * grid.y), FinishGeo{loss_out, inv_n, lambda_normal, lambda_dist}, s);
     return gsr_check_launch("loss_surfel_geo", s, false);
 }
 
@@ -503,9 +473,9 @@ __global__ void __launch_bounds__(256) k_plane_geo(PlaneGeoArgs p)
         for (int i = 0; i < GEO_NLD; i++) {
             const int e = threadIdx.x + i * 256, ly = e / GEO_PX, lx = e % GEO_PX, gy = y0 + ly - 2, gx = x0 + lx - 2;
             if (e < GEO_PX * GEO_PY) {
-                const float d = vd[i], fx = (float)gx, fy = (float)gy;
-                sP[0][ly][lx] = d * (fx * rm[0] + fy * rm[3] + rm[6]); sP[1][ly][lx] = d * (fx * rm[1] + fy * rm[4] + rm[7]);
-                sP[2][ly][lx] = d * (fx * rm[2] + fy * rm[5] + rm[8]);
+                float r[3];
+                geo_ray(rm, (float)gx, (float)gy, r);
+                sP[0][ly][lx] = vd[i] * r[0]; sP[1][ly][lx] = vd[i] * r[1]; sP[2][ly][lx] = vd[i] * r[2];
             }
         }
     }
@@ -516,22 +486,11 @@ __global__ void __launch_bounds__(256) k_plane_geo(PlaneGeoArgs p)
         if (gy >= 1 && gy <= H - 2 && gx >= 1 && gx <= W - 2) {
             const size_t o = (size_t)gy * W + gx;
             const float a = p.alpha[o], wl = p.wl * (p.weight ? p.weight[o] : 1.0f);
-            const int py = ly + 1, px = lx + 1;
-            float dx[3], dy[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) { dx[c] = sP[c][py + 1][px] - sP[c][py - 1][px]; dy[c] = sP[c][py][px + 1] - sP[c][py][px - 1]; }
-            const float c0 = dx[1] * dy[2] - dx[2] * dy[1], c1 = dx[2] * dy[0] - dx[0] * dy[2], c2 = dx[0] * dy[1] - dx[1] * dy[0];
-            const float len = sqrtf(c0 * c0 + c1 * c1 + c2 * c2);
-            const float inv = 1.0f / fmaxf(len, 1e-12f);
-            n[0] = c0 * inv; n[1] = c1 * inv; n[2] = c2 * inv;
-            float dn[3], dc[3];
+            float dx[3], dy[3], dn[3], len, inv;
+            geo_stencil(sP, ly + 1, lx + 1, dx, dy, n, len, inv);
 #pragma unroll
             for (int c = 0; c < 3; c++) dn[c] = wl * a * sgn_(a * n[c] - p.normal[c * N + o]);
-            const float nd = len > 1e-12f ? n[0] * dn[0] + n[1] * dn[1] + n[2] * dn[2] : 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; c++) dc[c] = (dn[c] - n[c] * nd) * inv;
-            g[0] = dy[1] * dc[2] - dy[2] * dc[1]; g[1] = dy[2] * dc[0] - dy[0] * dc[2]; g[2] = dy[0] * dc[1] - dy[1] * dc[0];
-            g[3] = dc[1] * dx[2] - dc[2] * dx[1]; g[4] = dc[2] * dx[0] - dc[0] * dx[2]; g[5] = dc[0] * dx[1] - dc[1] * dx[0];
+            geo_stencil_adjoint(dn, n, len, inv, dx, dy, g);
             n[0] *= a; n[1] *= a; n[2] *= a;
         }
 #pragma unroll
@@ -545,11 +504,10 @@ __global__ void __launch_bounds__(256) k_plane_geo(PlaneGeoArgs p)
     if (gx < W && gy < H) {
         const size_t o = (size_t)gy * W + gx;
         const int qy = ly + 1, qx = lx + 1;
-        float dP[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) dP[c] = sG[c][qy - 1][qx] - sG[c][qy + 1][qx] + sG[3 + c][qy][qx - 1] - sG[3 + c][qy][qx + 1];
-        const float fx = (float)gx, fy = (float)gy;
-        p.dDepth[o] = dP[0] * (fx * rm[0] + fy * rm[3] + rm[6]) + dP[1] * (fx * rm[1] + fy * rm[4] + rm[7]) + dP[2] * (fx * rm[2] + fy * rm[5] + rm[8]);
+        float dP[3], r[3];
+        geo_gather_dP(sG, qy, qx, dP);
+        geo_ray(rm, (float)gx, (float)gy, r);
+        p.dDepth[o] = dP[0] * r[0] + dP[1] * r[1] + dP[2] * r[2];
         const float w = p.weight ? p.weight[o] : 1.0f, wl = p.wl * w;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -581,7 +539,7 @@ extern "C" int gsr_loss_plane_geo(int32_t H, int32_t W, const float* plane_depth
     const dim3 grid(gsr_div_up(W, GEO_TX), gsr_div_up(H, GEO_TY));
     hipLaunchKernelGGL(k_plane_geo, grid, dim3(256), 0, s, a);
     // loss_out = {mean weighted L1, 0, lambda * mean}
-    hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(1024), 0, s, (const float2*)scratch, (int)(grid.x * grid.y), loss_out, inv_n, lambda_normal, 0.0f);
+    gsr_finish2((const float2*)scratch, (int)(grid.x * grid.y), FinishGeo{loss_out, inv_n, lambda_normal, 0.0f}, s);
     return gsr_check_launch("loss_plane_geo", s, false);
 }
 
@@ -609,11 +567,8 @@ __global__ void __launch_bounds__(256) k_scaling_prod(int64_t P, int cols, int s
         if (cols > 2) g[2] = wi * (x * y);
         for (int c = cols; c < stride; c++) g[c] = 0.f;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss_out, wgt * ((red[0] + red[1]) + (red[2] + red[3])));
+    const float tot = block_sum256(acc, red);
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_out, wgt * tot);
 }
 
 extern "C" int gsr_loss_scaling_prod(int64_t P, int32_t cols, int32_t stride, const float* scaling, const int32_t* count_dev, float lambda_scaling,

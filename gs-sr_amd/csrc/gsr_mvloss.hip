@@ -12,10 +12,12 @@
 //   k_mv_ncc : 16 lanes per sampled pixel.  Builds the plane-induced homography from the rendered normal / distance, walks the
 //              (2h+1)^2 patch twice (sums, then the chain rule back to the homography; 16-lane butterflies), writes ncc / mask and the
 //              UNSCALED gradients of sum(ncc * weight) to normal and distance at that pixel (sampled at most once: plain stores).
-//   k_mv_finish : {sum, count, sum/count (0 if count == 0)}.
+//   k_finish2<FinishMean> (gsr_reduce.h) : {sum, count, sum/count (0 if count == 0)}.
 // The means' 1/count and the lambdas are applied by the caller (gsrast.losses) as one device-scalar multiply in backward, so no
 // host synchronisation is needed anywhere.  Both kernels are gather-latency bound (random bilinear taps), not HBM-bound.
 #include "gsr_common.h"
+#include "gsr_reduce.h"
+#include "gsr_scan.h"
 
 __device__ __forceinline__ float3 mv_xform(const float* M, float3 p)
 {
@@ -25,15 +27,6 @@ __device__ __forceinline__ float3 mv_xform(const float* M, float3 p)
 __device__ __forceinline__ float3 mv_xform_t(const float* M, float3 d)      // d @ A^T
 {
     return make_float3(d.x * M[0] + d.y * M[1] + d.z * M[2], d.x * M[3] + d.y * M[4] + d.z * M[5], d.x * M[6] + d.y * M[7] + d.z * M[8]);
-}
-
-__device__ __forceinline__ float2 mv_block_sum2(float a, float b, float* red)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red[4 + (threadIdx.x >> 6)] = b; }
-    __syncthreads();
-    return make_float2((red[0] + red[1]) + (red[2] + red[3]), (red[4] + red[5]) + (red[6] + red[7]));
 }
 
 __global__ void __launch_bounds__(256) k_mv_geo(gsr_mv_cfg c, const float* __restrict__ depth, const float* __restrict__ near_depth,
@@ -94,7 +87,7 @@ __global__ void __launch_bounds__(256) k_mv_geo(gsr_mv_cfg c, const float* __res
         }
         g_depth[p] = gd;
     }
-    const float2 t = mv_block_sum2(s_w, s_c, red);
+    const float2 t = block_sum256(s_w, s_c, red);
     if (threadIdx.x == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 
@@ -244,24 +237,8 @@ __global__ void __launch_bounds__(256) k_mv_ncc(gsr_mv_cfg c, int N, const int32
         if (ncc_out) ncc_out[i] = 0.f;
         if (mask_out) mask_out[i] = 0;
     }
-    const float2 t = mv_block_sum2(s_v, s_c, red);
+    const float2 t = block_sum256(s_v, s_c, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-__global__ void __launch_bounds__(1024) k_mv_finish(const float2* __restrict__ partial, int n, float* stats)
-{
-    __shared__ float r1[16], r2[16];
-    float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < n; i += 1024) { const float2 q = partial[i]; a += q.x; b += q.y; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = a; r2[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < 16; w++) { sa += r1[w]; sb += r2[w]; }
-        stats[0] = sa; stats[1] = sb; stats[2] = sb > 0.f ? sa / sb : 0.f;
-    }
 }
 
 // The loss values and the gradient scaling of the two multi-view losses without a chain of scalar framework kernels (round 4: the wrapper spent
@@ -360,21 +337,15 @@ __global__ void __launch_bounds__(256) k_sm_hist(int64_t n, const uint8_t* __res
 template <int LEVEL>
 __global__ void __launch_bounds__(1024) k_sm_pick(const uint32_t* __restrict__ hist, uint32_t num, SmSel* sel)
 {
-    __shared__ uint32_t wsum[16];
+    __shared__ uint32_t lds[17];
     __shared__ uint32_t found_bin, found_below;
     if (threadIdx.x == 0) { found_bin = 4096u; found_below = 0u; }
     const uint32_t need = LEVEL ? num - sel->below0 : num;
     uint32_t v[4], t = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { v[e] = hist[threadIdx.x * 4 + e]; t += v[e]; }
-    uint32_t inc = t;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if ((threadIdx.x & 63) >= d) inc += o; }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-    uint32_t excl = woff + inc - t;
+    uint32_t all;
+    uint32_t excl = block_excl_scan(t, lds, &all);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (excl <= need && excl + v[e] > need) { found_bin = threadIdx.x * 4 + e; found_below = excl; }   // unique: prefixes are monotone
@@ -392,7 +363,7 @@ __global__ void __launch_bounds__(1024) k_sm_pick(const uint32_t* __restrict__ h
 }
 
 __global__ void __launch_bounds__(256) k_sm_count(int64_t n, const uint8_t* __restrict__ mask, uint32_t s0, uint32_t s1, const SmSel* __restrict__ sel,
-                                                  uint2* __restrict__ blockcnt)
+                                                  uint32_t* __restrict__ blockcnt /*[2][gridDim.x]: keys below T, keys equal to T*/)
 {
     __shared__ float red[8];
     const uint32_t T = sel->T24;
@@ -402,44 +373,17 @@ __global__ void __launch_bounds__(256) k_sm_count(int64_t n, const uint8_t* __re
         const int64_t p = base + it * 256 + threadIdx.x;
         if (p < n && mask[p]) { const uint32_t k = sm_key24((uint32_t)p, s0, s1); lt += k < T ? 1.f : 0.f; eq += k == T ? 1.f : 0.f; }
     }
-    const float2 t = mv_block_sum2(lt, eq, red);
-    if (threadIdx.x == 0) blockcnt[blockIdx.x] = make_uint2((uint32_t)t.x, (uint32_t)t.y);
-}
-
-__global__ void __launch_bounds__(1024) k_sm_scan(uint2* __restrict__ blockcnt, uint32_t nblk)
-{
-    __shared__ uint32_t wa[16], wb[16];
-    __shared__ uint32_t carry_a, carry_b;
-    if (threadIdx.x == 0) { carry_a = 0; carry_b = 0; }
-    __syncthreads();
-    for (uint32_t base = 0; base < nblk; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint2 v = i < nblk ? blockcnt[i] : make_uint2(0u, 0u);
-        uint32_t a = v.x, b = v.y;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t oa = __shfl_up(a, d, 64), ob = __shfl_up(b, d, 64);
-            if ((threadIdx.x & 63) >= d) { a += oa; b += ob; }
-        }
-        if ((threadIdx.x & 63) == 63) { wa[threadIdx.x >> 6] = a; wb[threadIdx.x >> 6] = b; }
-        __syncthreads();
-        uint32_t oa = carry_a, ob = carry_b;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) { oa += wa[w]; ob += wb[w]; }
-        if (i < nblk) blockcnt[i] = make_uint2(oa + a - v.x, ob + b - v.y);
-        __syncthreads();
-        if (threadIdx.x == 1023) { carry_a = oa + a; carry_b = ob + b; }
-        __syncthreads();
-    }
+    const float2 t = block_sum256(lt, eq, red);
+    if (threadIdx.x == 0) { blockcnt[blockIdx.x] = (uint32_t)t.x; blockcnt[gridDim.x + blockIdx.x] = (uint32_t)t.y; }
 }
 
 __global__ void __launch_bounds__(256) k_sm_write(int64_t n, const uint8_t* __restrict__ mask, uint32_t s0, uint32_t s1, const SmSel* __restrict__ sel,
-                                                  const uint2* __restrict__ blockoff, uint32_t num, int32_t* __restrict__ idx)
+                                                  const uint32_t* __restrict__ blockoff /*[2][gridDim.x]*/, uint32_t num, int32_t* __restrict__ idx)
 {
     __shared__ uint32_t wl[4], we[4];
     const uint32_t T = sel->T24;
     const uint32_t c_lt = sel->all ? 0xFFFFFFFFu : sel->c_lt;
-    const uint2 off = blockoff[blockIdx.x];
-    uint32_t run_l = off.x, run_e = off.y;
+    uint32_t run_l = blockoff[blockIdx.x], run_e = blockoff[gridDim.x + blockIdx.x];
     const int64_t base = (int64_t)blockIdx.x * SM_BLOCK;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int it = 0; it < SM_ITEMS; ++it) {
@@ -476,7 +420,7 @@ extern "C" int gsr_sample_mask(int64_t n, const uint8_t* mask, int32_t num, uint
     char* q = (char*)scratch;
     uint32_t* hist = (uint32_t*)q; q += gsr_align(2 * 4096 * sizeof(uint32_t));
     SmSel* sel = (SmSel*)q; q += gsr_align(sizeof(SmSel));
-    uint2* blockcnt = (uint2*)q;
+    uint32_t* blockcnt = (uint32_t*)q;                   // two planes of nblk words
     const uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32);
     const int64_t slots = n < (int64_t)num ? n : (int64_t)num;
     (void)gsr_memset_async(hist, 0, 2 * 4096 * sizeof(uint32_t), s);
@@ -486,8 +430,8 @@ extern "C" int gsr_sample_mask(int64_t n, const uint8_t* mask, int32_t num, uint
     hipLaunchKernelGGL(k_sm_hist<1>, dim3(nblk), dim3(256), 0, s, n, mask, s0, s1, (const SmSel*)sel, hist + 4096);
     hipLaunchKernelGGL(k_sm_pick<1>, dim3(1), dim3(1024), 0, s, (const uint32_t*)(hist + 4096), (uint32_t)num, sel);
     hipLaunchKernelGGL(k_sm_count, dim3(nblk), dim3(256), 0, s, n, mask, s0, s1, (const SmSel*)sel, blockcnt);
-    hipLaunchKernelGGL(k_sm_scan, dim3(1), dim3(1024), 0, s, blockcnt, nblk);
-    hipLaunchKernelGGL(k_sm_write, dim3(nblk), dim3(256), 0, s, n, mask, s0, s1, (const SmSel*)sel, (const uint2*)blockcnt, (uint32_t)slots, idx_out);
+    gsr_scan_small(blockcnt, nblk, 2, nblk, nullptr, nullptr, s);
+    hipLaunchKernelGGL(k_sm_write, dim3(nblk), dim3(256), 0, s, n, mask, s0, s1, (const SmSel*)sel, (const uint32_t*)blockcnt, (uint32_t)slots, idx_out);
     return gsr_check_launch("sample_mask", s, false);
 }
 
@@ -516,7 +460,7 @@ extern "C" int gsr_loss_plane_mv_geo(const gsr_mv_cfg* cfg, const float* plane_d
     const dim3 grid(gsr_div_up(cfg->W, 32), gsr_div_up(cfg->H, 8));
     (void)gsr_memset_async(g_near, 0, sizeof(float) * (size_t)cfg->Wn * cfg->Hn, s);
     hipLaunchKernelGGL(k_mv_geo, grid, dim3(256), 0, s, *cfg, plane_depth, near_plane_depth, noise, d_mask, weight, g_depth, g_near, (float2*)scratch);
-    hipLaunchKernelGGL(k_mv_finish, dim3(1), dim3(1024), 0, s, (const float2*)scratch, (int)(grid.x * grid.y), stats);
+    gsr_finish2((const float2*)scratch, (int)(grid.x * grid.y), FinishMean{stats}, s);
     return gsr_check_launch("loss_plane_mv_geo", s, false);
 }
 
@@ -541,6 +485,6 @@ extern "C" int gsr_loss_plane_mv_ncc(const gsr_mv_cfg* cfg, int32_t n_samples, c
     else
         hipLaunchKernelGGL(k_mv_ncc<false>, dim3(blocks), dim3(256), 0, s, *cfg, (int)n_samples, idx, weight, normal, distance, gray, near_gray, ncc, mask,
                            g_normal, g_distance, (float2*)scratch);
-    hipLaunchKernelGGL(k_mv_finish, dim3(1), dim3(1024), 0, s, (const float2*)scratch, blocks, stats);
+    gsr_finish2((const float2*)scratch, blocks, FinishMean{stats}, s);
     return gsr_check_launch("loss_plane_mv_ncc", s, false);
 }

@@ -209,7 +209,7 @@ def test_training_stats_at_the_block_edge(Nv):
 def test_beyond_every_grid_cap_and_scan_sweep():
     """Nv >= 270 000 visible anchors: more than 131 072 rows for stage 1 (2048 blocks x 4 tiles x 16), 65 536 for the emit kernel, 32 768 for the
     backward heads -- every tile kernel takes its grid-stride loop again; 264+ scan workgroups, i.e. more than 64 look-back predecessors (the q += 64
-    step); more than 1024 block sums in k_stats_scan.  Truth: the float64 chain run by torch on the device; floor: the float32 chain there.  The case leaves out the
+    step); more than 1024 block sums for the statistics scan (k_scan_small: two per thread).  Truth: the float64 chain run by torch on the device; floor: the float32 chain there.  The case leaves out the
     anchors whose float64 hidden pre-activations touch the ReLU kink (decode_truth.large_case says why and what was measured with them in)."""
     case = decode_truth.large_case()
     Nv = case["vis_idx"].size

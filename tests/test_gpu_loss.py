@@ -17,7 +17,8 @@ def _pair(shape, seed, noise=0.15):
 
 
 @pytest.mark.parametrize("shape,lam", [((3, 37, 53), 0.2), ((1, 8, 9), 0.5), ((3, 64, 48), 1.0), ((2, 11, 30), 0.0), ((3, 16, 16), 0.2),
-                                       ((3, 1, 1), 0.2), ((3, 200, 333), 0.2)])
+                                       ((3, 1, 1), 0.2), ((3, 200, 333), 0.2),
+                                       ((8200, 2, 2), 0.2)])                # one block per channel: 8200 partials, the finish kernel's second trip
 def test_l1_ssim_matches_oracle(shape, lam):
     from gsrast.losses import l1_ssim
     img, gt = _pair(shape, sum(shape))
@@ -58,7 +59,8 @@ def _geo_inputs(H, W, seed):
 
 
 @pytest.mark.parametrize("H,W,ratio,seed", [(23, 31, 0.0, 0), (17, 40, 1.0, 1), (30, 22, 0.3, 2), (3, 3, 0.0, 3), (2, 5, 0.0, 4), (16, 16, 0.0, 5),
-                                            (33, 49, 0.0, 6), (200, 333, 0.0, 7)])
+                                            (33, 49, 0.0, 6), (200, 333, 0.0, 7),
+                                            (32772, 3, 0.0, 8)])           # 8193 blocks of 64 x 4: the finish kernel's second trip
 def test_surfel_geo_matches_oracle(H, W, ratio, seed):
     from gsrast.losses import camera_ray_matrices, surfel_geo_loss
     am, wvt, fpt = _geo_inputs(H, W, seed)
@@ -95,7 +97,8 @@ def test_surfel_geo_full_hd_vs_torch_chain():
     assert ((g - gr).norm() / gr.norm()).item() < 2e-3        # fp32 chain vs fp32 fused: cancellation in the cross products
 
 
-@pytest.mark.parametrize("H,W,seed,use_w", [(23, 31, 0, True), (17, 40, 1, False), (3, 3, 2, True), (2, 6, 3, True), (100, 161, 4, True)])
+@pytest.mark.parametrize("H,W,seed,use_w", [(23, 31, 0, True), (17, 40, 1, False), (3, 3, 2, True), (2, 6, 3, True), (100, 161, 4, True),
+                                            (32772, 3, 5, True)])           # 8193 blocks of 64 x 4: the finish kernel's second trip
 def test_plane_geo_matches_oracle(H, W, seed, use_w):
     import test_loss_cpu
     from gsrast.losses import plane_geo_loss

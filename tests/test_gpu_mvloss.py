@@ -120,6 +120,33 @@ def test_multiview_sampling_and_empty_masks():
     assert all(np.isfinite(v).all() and not v.any() for v in g.values())
 
 
+def test_multiview_finish_beyond_8192_partials():
+    """2048 x 1088: k_mv_geo's grid is 64 x 136 = 8704 blocks, so the finish kernel's load loop takes its second trip.  Every summand passes
+    through fewer than 64 float32 additions of non-negative terms (1 + 9 per thread, 6 + 3 per block, 6 + 16 in the finish): 64 x 2^-24 = 3.8e-6."""
+    case = mv_cases.plane_pair(W=2048, H=1088, seed=13, amp=0.002, tex=25.0)
+    geo, ncc, aux, g = _run_hip(case, num_sample=256)
+    stats, dm = aux["stats"], aux["d_mask"]
+    assert dm.sum() > 8704
+    assert stats[1] == dm.sum()                                              # integers below 2^24: exact
+    truth = (aux["weights"].astype(np.float64) * aux["pixel_noise"].astype(np.float64))[dm].sum()
+    np.testing.assert_allclose(stats[0], truth, rtol=1e-5)
+    assert stats[2] == np.float32(stats[0]) / np.float32(stats[1])
+    assert np.float32(geo) == np.float32(0.03) * stats[2]
+
+
+def test_sampler_beyond_1024_block_sums():
+    """2049 x 2049 = 4 198 401 entries: 1026 blocks of 4096, more block sums than one pass of the scan's 1024 threads."""
+    from gsrast.losses import sample_valid_pixels
+    mask = np.random.default_rng(21).random(2049 * 2049) < 0.5
+    dm = torch.tensor(mask, device=DEV)
+    s1 = sample_valid_pixels(dm, 5000, seed=11).cpu().numpy(); s1b = sample_valid_pixels(dm, 5000, seed=11).cpu().numpy()
+    s2 = sample_valid_pixels(dm, 5000, seed=12).cpu().numpy()
+    assert np.array_equal(s1, s1b) and not np.array_equal(s1, s2)
+    for sset in (s1, s2):
+        assert sset.size == 5000 and (sset >= 0).all() and np.unique(sset).size == 5000 and mask[sset].all()
+        assert (np.diff(sset[:4990]) > 0).all()                              # ascending (the last few slots may hold threshold ties)
+
+
 def test_multiview_full_hd_vs_torch_chain():
     """1920x1080, 102400 sampled patches: fused kernels vs the torch op chain on the same device and the same sample set."""
     import ref_mv_torch

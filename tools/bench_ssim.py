@@ -1,4 +1,4 @@
-"""Times the fused L1+SSIM loss (gsrast.losses.l1_ssim: k_ssim_fwd + k_ssim_bwd + k_ssim_finish) at 3 x 1080 x 1920: ms per call, value + gradient."""
+"""Times the fused L1+SSIM loss (gsrast.losses.l1_ssim: k_ssim_fwd + k_ssim_bwd + k_finish2<FinishSsim>) at 3 x 1080 x 1920: ms per call, value + gradient."""
 import json
 import os
 import sys
