@@ -170,18 +170,14 @@ def test_scaffold_iteration_replayed_from_a_graph_tracks_the_eager_one():
     """The complete scaffold-2dgs iteration (prefilter, decode, surfel rasterizer, L1+SSIM + normal / distortion + scaling losses, backward,
     densification statistics, fused Adam) recorded once with gsrast.graphs.GraphedStep and replayed: parameters and statistics after the same
     number of iterations agree with the eager, reference-shaped iteration (differences: float-atomic order only)."""
-    import os
-    import sys
-    import types
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import bench_pipeline
+    from gsrast import methods
     from gsrast.graphs import GraphedStep
     dev = torch.device("cuda:0")
     n_warm, n_run = 3, 4
-    e_step, e_st = bench_pipeline.build(types.SimpleNamespace(decode="hip", loss="full-hip", Na=9000), dev)
+    e_step, e_st = methods.build("scaffold-2dgs", dev, Na=9000)
     for _ in range(n_warm + n_run):
         e_step()
-    g_step, g_st = bench_pipeline.build(types.SimpleNamespace(decode="hip", loss="full-hip", Na=9000, static=True), dev)
+    g_step, g_st = methods.build("scaffold-2dgs", dev, static=True, Na=9000)
     it = GraphedStep(g_step, optimizers=g_st["optimizers"], warmup=n_warm)
     for _ in range(n_run):
         it()

@@ -1,12 +1,11 @@
 """Bisects the graph-replayed scaffold-2dgs iteration: records growing prefixes of it and compares each replay with the eager result."""
-import os, sys, types, torch
+import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import bench_pipeline
+sys.path.insert(0, os.path.join(ROOT, "gs-sr_amd"))
+from gsrast import methods
 dev = torch.device("cuda:0")
 for stop in ("prefilter", "decode", "raster", "loss", "backward"):
-    a = types.SimpleNamespace(decode="hip", loss="full-hip", Na=9000, static=True, stop_after=stop)
-    step, st = bench_pipeline.build(a, dev)
+    step, st = methods.build("scaffold-2dgs", dev, static=True, Na=9000, stop_after=stop)
     ref = step()
     torch.cuda.synchronize()
     s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
@@ -30,8 +29,7 @@ from gsrast import rasterize as rz
 for stop in ("stats", "step", None):
     outs = {}
     for mode in ("eager", "graph"):
-        a = types.SimpleNamespace(decode="hip", loss="full-hip", Na=9000, static=True, stop_after=stop)
-        step, st = bench_pipeline.build(a, dev)
+        step, st = methods.build("scaffold-2dgs", dev, static=True, Na=9000, stop_after=stop)
         opt = st["optimizers"][0]
         pars = [p for g in opt.param_groups for p in g["params"]]
         if mode == "eager":

@@ -1,11 +1,11 @@
-"""Host time per octree-pgsr iteration with the device queue never full: python tools/host_time_octree.py (GSR_PIPE_SHADOWS=0/1)."""
-import os, sys, time, types, cProfile, pstats
+"""Host time per octree-pgsr iteration with the device queue never full: python tools/host_time_octree.py
+(eager gsrast.methods.octree_pgsr; every iteration is synchronised, then profiled by cumulative host time)."""
+import os, sys, time, cProfile, pstats
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "gs-sr_amd"))
 import torch
-import bench_pipeline_octree_pgsr as bp
-a = types.SimpleNamespace(Na=74000, static=False)
-step, st = bp.build(a, torch.device("cuda:0"))
+from gsrast import methods
+step, st = methods.build("octree-pgsr", torch.device("cuda:0"))
 for _ in range(10):
     step()
 torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 """GPU-kernel time vs wall time of one complete method iteration (scaffold-2dgs = configs[1], octree/vanilla-pgsr = configs[2]).
-Runs the tools/bench_pipeline*.py iteration under torch.profiler (roctracer sees every HIP kernel of the process, including the
+Runs the gsrast.methods iteration under torch.profiler (roctracer sees every HIP kernel of the process, including the
 ones launched through the C ABI) and reports per iteration: wall ms, summed kernel ms, kernel launches, and the kernels by total time."""
 import argparse
 import collections
@@ -7,12 +7,11 @@ import json
 import os
 import sys
 import time
-import types
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "gs-sr_amd"))
 
 
 def measure(step, dev, steps=20, warmup=8, top=14):
@@ -50,17 +49,9 @@ def main():
     ap.add_argument("--method", default="scaffold-2dgs", choices=["scaffold-2dgs", "octree-2dgs", "pgsr", "octree-pgsr"])
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
+    from gsrast import methods
     dev = torch.device("cuda:0")
-    if a.method in ("scaffold-2dgs", "octree-2dgs"):
-        import bench_pipeline
-        lod = a.method == "octree-2dgs"
-        step, st = bench_pipeline.build(types.SimpleNamespace(decode="hip", loss="full-hip", Na=87000 if lod else 72000, lod=lod), dev)
-    elif a.method == "octree-pgsr":
-        import bench_pipeline_octree_pgsr
-        step, st = bench_pipeline_octree_pgsr.build(types.SimpleNamespace(Na=74000), dev)
-    else:
-        import bench_pipeline_pgsr
-        step, st = bench_pipeline_pgsr.build(types.SimpleNamespace(glue="hip", P=300000), dev)
+    step, st = methods.build(a.method, dev)
     r = measure(step, dev, steps=a.steps)
     r["method"] = a.method
     print(json.dumps(r))

@@ -1,14 +1,8 @@
 """Per-iteration GPU time of the torch glue ops (zero fills, scalar multiplies, gradient accumulation adds ...) around the HIP kernels of a\ncomplete method iteration, grouped by op and input shape:  python tools/prof_glue.py octree|scaffold"""
-import sys, os, types, torch
-sys.path.insert(0, "tools")
-which = sys.argv[1]
-dev = torch.device("cuda:0")
-if which == "octree":
-    import bench_pipeline_octree_pgsr as b
-    step, st = b.build(types.SimpleNamespace(Na=74000), dev)
-else:
-    import bench_pipeline as b
-    step, st = b.build(types.SimpleNamespace(decode="hip", loss="full-hip", Na=72000), dev)
+import sys, os, torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gs-sr_amd"))
+from gsrast import methods
+step, st = methods.build("octree-pgsr" if sys.argv[1] == "octree" else "scaffold-2dgs", torch.device("cuda:0"))
 for _ in range(8): step()
 from torch.profiler import profile, ProfilerActivity
 with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU], record_shapes=True, with_stack=False) as prof:

@@ -1,11 +1,11 @@
 """Distribution of tile-list lengths in the method pipelines (which path of the per-tile depth sort they take):
-    python tools/tile_list_lengths.py [octree-pgsr|scaffold-2dgs]"""
-import json, os, sys, types
+    python tools/tile_list_lengths.py [octree-pgsr|scaffold-2dgs|octree-2dgs|pgsr]"""
+import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "gs-sr_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "gs-sr_amd"))
 import numpy as np
 import torch
-from gsrast import rasterize as rz
+from gsrast import methods, rasterize as rz
 
 which = sys.argv[1] if len(sys.argv) > 1 else "octree-pgsr"
 seen = []
@@ -33,13 +33,7 @@ rz.forward = spy
 for m in list(sys.modules.values()):
     if m is not None and getattr(m, "__name__", "").startswith("diff_") and hasattr(m, "rz"):
         pass
-if which == "octree-pgsr":
-    import bench_pipeline_octree_pgsr as bp
-    step, st = bp.build(types.SimpleNamespace(Na=74000, static=False), torch.device("cuda:0"))
-else:
-    import bench_pipeline as bp
-    ns = types.SimpleNamespace(Na=72000, static=False, decode="hip", loss="bench", stop_after=None, graph=False, lod=False)
-    step, st = bp.build(ns, torch.device("cuda:0"))
+step, st = methods.build(which, torch.device("cuda:0"))
 step()
 torch.cuda.synchronize()
 for s in seen:
