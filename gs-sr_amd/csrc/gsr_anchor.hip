@@ -10,12 +10,16 @@
 // This unit is built with -ffp-contract=off: the cell of a point is an integer output and must not depend on FMA contraction.
 #include "gsr_common.h"
 #include "gsr_scan.h"
+#include <cmath>
 #include <vector>
 
 #define ANC_BLOCK 1024
 #define ANC_BIAS 1048576            // 2^20: cells in [-2^20, 2^20 - 1] per axis
 #define ANC_CNT_ENTRIES 0           // counters: entries in the sort
 #define ANC_CNT_HEADS 1             //           new anchors
+#define ANC_CNT_FOUND 2             //           new anchors before the weed-out (gsr_anchor_level_find_weed)
+#define WEED_BLOCK 256
+#define WEED_CHUNK GSR_OCTREE_WEED_CHUNK      // cameras staged in LDS at a time (16 bytes each)
 
 // ---------------------------------------------------------------------------------------------------------------- entries of a level
 // c = rint((p - origin) / cell): round-half-even, IEEE division (no reciprocal), every operation rounded on its own
@@ -31,12 +35,13 @@ __device__ __forceinline__ bool anc_cell_key(float px, float py, float pz, const
 }
 
 // Entry i of the level: i < Na the cell of anchor i (tag 0), otherwise candidate slot i - Na (tag 1).  Returns whether the entry takes part.
-__device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L, uint64_t* key, uint32_t* status)
+// occupy [N0] (Octree-GS: occupancy apart from candidacy) or NULL: an original anchor occupies its cell iff occupy[i], where NULL iff the mask admits it.
+__device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L, const uint8_t* __restrict__ occupy, uint64_t* key, uint32_t* status)
 {
     const uint32_t Na = (uint32_t)L.Na, N0 = (uint32_t)L.N0;
     uint64_t k63;
     if (i < Na) {
-        if (i < N0 && L.mask && !L.mask[i]) return false;
+        if (i < N0 && (occupy ? !occupy[i] : (L.mask && !L.mask[i]))) return false;
         // an anchor outside the packing range cannot share a cell with a candidate inside it: it is left out, not an error
         if (!anc_cell_key(L.anchor[3 * (size_t)i], L.anchor[3 * (size_t)i + 1], L.anchor[3 * (size_t)i + 2], L, &k63)) return false;
         *key = k63 << 1;
@@ -55,25 +60,26 @@ __device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L,
     return true;
 }
 
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_count(gsr_anchor_level L, uint32_t cap, uint32_t* __restrict__ sums, uint32_t* __restrict__ status)
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_count(gsr_anchor_level L, const uint8_t* __restrict__ occupy, uint32_t cap, uint32_t* __restrict__ sums,
+                                                               uint32_t* __restrict__ status)
 {
     __shared__ uint32_t lds[17];
     const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
     uint64_t key;
-    const uint32_t f = (i < cap && anc_entry(i, L, &key, status)) ? 1u : 0u;
+    const uint32_t f = (i < cap && anc_entry(i, L, occupy, &key, status)) ? 1u : 0u;
     uint32_t tot;
     block_excl_scan(f, lds, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_place(gsr_anchor_level L, uint32_t cap, const uint32_t* __restrict__ sums, uint32_t* __restrict__ status,
-                                                               uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi, uint32_t* __restrict__ sort_keys,
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_place(gsr_anchor_level L, const uint8_t* __restrict__ occupy, uint32_t cap,
+                                                               const uint32_t* __restrict__ sums, uint32_t* __restrict__ status, uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi, uint32_t* __restrict__ sort_keys,
                                                                uint32_t* __restrict__ src)
 {
     __shared__ uint32_t lds[17];
     const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
     uint64_t key = 0;
-    const bool f = i < cap && anc_entry(i, L, &key, status);
+    const bool f = i < cap && anc_entry(i, L, occupy, &key, status);
     uint32_t tot;
     const uint32_t pos = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);       // < cap: at most one position per entry
     if (f) { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
@@ -121,6 +127,111 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_place(const uint32_t* __
 __global__ void __launch_bounds__(64) k_anc_publish(const uint32_t* __restrict__ counters, uint32_t* __restrict__ status)
 {
     if (threadIdx.x == 0) status[0] = counters[ANC_CNT_HEADS];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Octree-GS weed-out
+// OctreeGaussian.weed_out (octree_gaussian.py:203-214): the number of cameras that would show a new anchor of level lv at p.  Per camera
+//   d = sqrt(((dx^2 + dy^2) + dz^2)) * scale;  pred = log2(standard_dist / d) / log2(fork);  il = clamp(floor | rint | ceil (pred), 0, levels - 1)
+// in float32, every operation rounded on its own (this unit is built without FMA contraction), the clamp applied before the conversion.
+// The whole block calls this: cameras are staged through LDS in chunks of WEED_CHUNK and every lane reads the same address (a broadcast).
+struct WeedArgs { const float* cam; int32_t C, levels, mode; float standard_dist, log2_fork, visible_threshold; };
+
+__device__ __forceinline__ uint32_t weed_visible(bool active, float px, float py, float pz, int32_t lv, const WeedArgs& W, float4* cams)
+{
+    uint32_t visible = 0;
+    const float top = (float)(W.levels - 1);
+    for (int32_t c0 = 0; c0 < W.C; c0 += WEED_CHUNK) {
+        const int32_t nc = min(WEED_CHUNK, W.C - c0);
+        for (int32_t c = threadIdx.x; c < nc; c += blockDim.x) {
+            const float* q = W.cam + 4 * (size_t)(c0 + c);
+            cams[c] = make_float4(q[0], q[1], q[2], q[3]);
+        }
+        __syncthreads();
+        if (active) {
+            for (int32_t c = 0; c < nc; c++) {
+                const float4 cam = cams[c];
+                const float dx = px - cam.x, dy = py - cam.y, dz = pz - cam.z;
+                const float d = __fsqrt_rn((dx * dx + dy * dy) + dz * dz) * cam.w;
+                const float pred = __fdiv_rn(log2f(__fdiv_rn(W.standard_dist, d)), W.log2_fork);
+                float r = W.mode == 0 ? floorf(pred) : (W.mode == 1 ? rintf(pred) : ceilf(pred));
+                r = fminf(fmaxf(r, 0.0f), top);                     // the clamp, before the conversion
+                visible += (lv <= (int32_t)r) ? 1u : 0u;
+            }
+        }
+        __syncthreads();
+    }
+    return visible;
+}
+__device__ __forceinline__ bool weed_keep(uint32_t visible, const WeedArgs& W)
+{
+    return __fdiv_rn((float)visible, (float)W.C) > W.visible_threshold;
+}
+
+__global__ void __launch_bounds__(WEED_BLOCK) k_weed_rows(WeedArgs W, uint32_t U, const float* __restrict__ pos, const int32_t* __restrict__ level,
+                                                          int32_t* __restrict__ visible_count, uint8_t* __restrict__ keep)
+{
+    __shared__ float4 cams[WEED_CHUNK];
+    const uint32_t i = blockIdx.x * WEED_BLOCK + threadIdx.x;
+    const bool active = i < U;
+    float px = 0.f, py = 0.f, pz = 0.f; int32_t lv = 0;
+    if (active) { px = pos[3 * (size_t)i]; py = pos[3 * (size_t)i + 1]; pz = pos[3 * (size_t)i + 2]; lv = level[i]; }
+    const uint32_t v = weed_visible(active, px, py, pz, lv, W, cams);
+    if (active) { visible_count[i] = (int32_t)v; keep[i] = weed_keep(v, W) ? 1 : 0; }
+}
+
+// One thread per numbered head: flag[q] = the cell's position survives the weed-out; head_pos is copied to `heads` so that the compaction can
+// write it back in place.  The head count is read on the device; the grid covers the worst case and surplus blocks leave.
+__global__ void __launch_bounds__(WEED_BLOCK) k_anc_weed_flag(gsr_anchor_level L, WeedArgs W, int32_t lv, const uint32_t* __restrict__ counters,
+                                                              const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_lo,
+                                                              const uint32_t* __restrict__ head_pos, uint32_t* __restrict__ heads, uint32_t* __restrict__ flag)
+{
+    __shared__ float4 cams[WEED_CHUNK];
+    const uint32_t n_heads = counters[ANC_CNT_HEADS];
+    if (blockIdx.x * WEED_BLOCK >= n_heads) return;                 // the whole block
+    const uint32_t q = blockIdx.x * WEED_BLOCK + threadIdx.x;
+    const bool active = q < n_heads;
+    float px = 0.f, py = 0.f, pz = 0.f;
+    uint32_t p = 0;
+    if (active) {
+        p = head_pos[q];
+        const uint64_t cellkey = (((uint64_t)hi[p] << 32) | key_lo[perm[p]]) >> 1;
+        const int cx = (int)((cellkey >> 42) & 0x1FFFFFu) - ANC_BIAS, cy = (int)((cellkey >> 21) & 0x1FFFFFu) - ANC_BIAS, cz = (int)(cellkey & 0x1FFFFFu) - ANC_BIAS;
+        const float ax = (float)cx * L.cell, ay = (float)cy * L.cell, az = (float)cz * L.cell;       // as k_anc_emit writes it
+        px = ax + L.origin[0]; py = ay + L.origin[1]; pz = az + L.origin[2];
+    }
+    const uint32_t v = weed_visible(active, px, py, pz, lv, W, cams);
+    if (active) { heads[q] = p; flag[q] = weed_keep(v, W) ? 1u : 0u; }
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_weed_count(const uint32_t* __restrict__ counters, const uint32_t* __restrict__ flag, uint32_t* __restrict__ sums)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t q = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    uint32_t tot;
+    block_excl_scan((q < counters[ANC_CNT_HEADS] && flag[q]) ? 1u : 0u, lds, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(ANC_BLOCK) k_anc_weed_place(const uint32_t* __restrict__ counters, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ heads,
+                                                              const uint32_t* __restrict__ sums, uint32_t* __restrict__ head_pos)
+{
+    __shared__ uint32_t lds[17];
+    const uint32_t q = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    const bool f = q < counters[ANC_CNT_HEADS] && flag[q];
+    uint32_t tot;
+    const uint32_t w = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);        // w <= q < capacity
+    if (f) head_pos[w] = heads[q];
+}
+
+// the weeded count takes the place of the head count (gsr_anchor_level_emit reads it); status = {final, overflow (sticky), found before the weed-out}
+__global__ void __launch_bounds__(64) k_anc_publish_weed(uint32_t* __restrict__ counters, uint32_t* __restrict__ status, int weeded)
+{
+    if (threadIdx.x == 0) {
+        const uint32_t found = counters[ANC_CNT_HEADS];
+        if (weeded) counters[ANC_CNT_HEADS] = counters[ANC_CNT_FOUND];
+        status[0] = counters[ANC_CNT_HEADS];
+        status[2] = found;
+    }
 }
 
 // new_anchor = float(c) * cell + origin (a multiply, then an add); new_feat = element-wise maximum of anchor_feat over the run's candidates
@@ -195,20 +306,36 @@ extern "C" size_t gsr_anchor_level_scratch_bytes(int32_t Na, int32_t N0, int32_t
     return anc_carve((uint32_t)c, nullptr).bytes;
 }
 
-extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, size_t scratch_bytes, uint32_t* status_dev, void* stream)
+static int weed_check(const gsr_octree_weed* w, const char* who, WeedArgs* W)
+{
+    if (!w) { gsr_set_error("%s: weed is NULL", who); return 1; }
+    if (w->C < 1 || !w->cam_infos) { gsr_set_error("%s: cam_infos must hold at least one camera", who); return 1; }
+    if (w->levels < 1) { gsr_set_error("%s: levels=%d must be >= 1", who, w->levels); return 1; }
+    if (w->mode == 3) { gsr_set_error("%s: dist2level 'progressive' is not supported by the weed-out", who); return 1; }
+    if (w->mode < 0 || w->mode > 2) { gsr_set_error("%s: Unknown dist2level: %d", who, w->mode); return 1; }
+    if (!(w->fork > 1.0f) || !(w->standard_dist > 0.0f)) { gsr_set_error("%s: fork must exceed 1 and standard_dist must be positive", who); return 1; }
+    *W = {w->cam_infos, w->C, w->levels, w->mode, w->standard_dist, (float)log2((double)w->fork), w->visible_threshold};
+    return 0;
+}
+
+// three_words: the caller's status_dev holds the third word (found before the weed-out); gsr_anchor_level_find's holds two
+static int anc_find(const char* who, const gsr_anchor_level* lv, const uint8_t* occupy, const gsr_octree_weed* weed, bool three_words, void* scratch,
+                    size_t scratch_bytes, uint32_t* status_dev, void* stream)
 {
     uint32_t cap;
-    if (anc_check(lv, "anchor_level_find", &cap)) return 1;
-    if (!status_dev) { gsr_set_error("anchor_level_find: status_dev is NULL"); return 1; }
+    WeedArgs W = {};
+    if (anc_check(lv, who, &cap)) return 1;
+    if (weed && weed_check(weed, who, &W)) return 1;
+    if (!status_dev) { gsr_set_error("%s: status_dev is NULL", who); return 1; }
     const AncScratch a = anc_carve(cap, scratch);
-    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("anchor_level_find: scratch too small: %zu < %zu", scratch_bytes, a.bytes); return 1; }
+    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, a.bytes); return 1; }
     hipStream_t s = (hipStream_t)stream;
-    if (gsr_memset_async(a.counters, 0, 64, s)) { gsr_set_error("anchor_level_find: counters"); return 1; }
+    if (gsr_memset_async(a.counters, 0, 64, s)) { gsr_set_error("%s: counters", who); return 1; }
     if (cap) {
         const uint32_t nblk = gsr_div_up(cap, ANC_BLOCK);
-        hipLaunchKernelGGL(k_anc_entry_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev);
+        hipLaunchKernelGGL(k_anc_entry_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, occupy, cap, a.sums, status_dev);
         gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_ENTRIES, nullptr, s);
-        hipLaunchKernelGGL(k_anc_entry_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, cap, a.sums, status_dev, a.key_lo, a.key_hi, a.ka, a.src);
+        hipLaunchKernelGGL(k_anc_entry_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, occupy, cap, a.sums, status_dev, a.key_lo, a.key_hi, a.ka, a.src);
         const uint32_t* n_dev = a.counters + ANC_CNT_ENTRIES;
         uint32_t *k0 = a.ka, *v0 = a.va, *k1 = a.kb, *v1 = a.vb;
         bool in_b = false;
@@ -218,13 +345,50 @@ extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, 
         if (gsr_radix_sort_pairs(k0, v0, k1, v1, cap, n_dev, 0, 32, 8, false, a.hist, &in_b, s)) return 1;
         if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
         // both sorts run 4 passes of 8 bits: the order ends in (ka, va), the run heads go to kb -- gsr_anchor_level_emit relies on it
-        if (k0 != a.ka || v0 != a.va) { gsr_set_error("anchor_level_find: unexpected sort buffer parity"); return 1; }
+        if (k0 != a.ka || v0 != a.va) { gsr_set_error("%s: unexpected sort buffer parity", who); return 1; }
         hipLaunchKernelGGL(k_anc_head_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums);
         gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_HEADS, nullptr, s);
         hipLaunchKernelGGL(k_anc_head_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums, a.kb);
+        if (weed) {
+            // heads <= candidate slots; key_hi (consumed by the gather) keeps the unweeded heads, vb (free: the order ended in ka / va) the flags
+            const uint32_t worst = (uint32_t)lv->N0 * (uint32_t)lv->k;
+            if (worst) {
+                hipLaunchKernelGGL(k_anc_weed_flag, dim3(gsr_div_up(worst, WEED_BLOCK)), dim3(WEED_BLOCK), 0, s, *lv, W, weed->lv, a.counters, a.ka, a.va, a.key_lo,
+                                   a.kb, a.key_hi, a.vb);
+                hipLaunchKernelGGL(k_anc_weed_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, a.counters, a.vb, a.sums);
+                gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_FOUND, nullptr, s);
+                hipLaunchKernelGGL(k_anc_weed_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, a.counters, a.vb, a.key_hi, a.sums, a.kb);
+            }
+        }
     }
-    hipLaunchKernelGGL(k_anc_publish, dim3(1), dim3(64), 0, s, a.counters, status_dev);
-    return gsr_check_launch("anchor_level_find", s, false);
+    if (three_words) hipLaunchKernelGGL(k_anc_publish_weed, dim3(1), dim3(64), 0, s, a.counters, status_dev, (weed && cap && lv->N0) ? 1 : 0);
+    else hipLaunchKernelGGL(k_anc_publish, dim3(1), dim3(64), 0, s, a.counters, status_dev);
+    return gsr_check_launch(who, s, false);
+}
+
+extern "C" int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, size_t scratch_bytes, uint32_t* status_dev, void* stream)
+{
+    return anc_find("anchor_level_find", lv, nullptr, nullptr, false, scratch, scratch_bytes, status_dev, stream);
+}
+
+extern "C" int gsr_anchor_level_find_weed(const gsr_anchor_level* lv, const uint8_t* occupy, const gsr_octree_weed* weed, void* scratch, size_t scratch_bytes,
+                                          uint32_t* status_dev, void* stream)
+{
+    return anc_find("anchor_level_find_weed", lv, occupy, weed, true, scratch, scratch_bytes, status_dev, stream);
+}
+
+extern "C" int gsr_octree_weed_out(const float* positions, const int32_t* levels, int64_t U, const gsr_octree_weed* weed, int32_t* visible_count, uint8_t* keep,
+                                   void* stream)
+{
+    const char* who = "octree_weed_out";
+    WeedArgs W;
+    if (weed_check(weed, who, &W)) return 1;
+    if (U < 0 || U >= (1ll << 31)) { gsr_set_error("%s: U=%lld out of range", who, (long long)U); return 1; }
+    if (U == 0) return 0;
+    if (!positions || !levels || !visible_count || !keep) { gsr_set_error("%s: positions / levels / visible_count / keep is NULL", who); return 1; }
+    hipLaunchKernelGGL(k_weed_rows, dim3(gsr_div_up((uint32_t)U, WEED_BLOCK)), dim3(WEED_BLOCK), 0, (hipStream_t)stream, W, (uint32_t)U, positions, levels,
+                       visible_count, keep);
+    return gsr_check_launch(who, (hipStream_t)stream, false);
 }
 
 extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scratch, size_t scratch_bytes, uint32_t count, float* new_anchor, float* new_feat,

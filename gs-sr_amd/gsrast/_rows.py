@@ -15,6 +15,29 @@ class Level(C.Structure):                 # include/gsrast.h gsr_anchor_level
                 ("anchor", _vp), ("mask", _vp), ("offset", _vp), ("scaling", _vp), ("anchor_feat", _vp), ("grads", _vp), ("offset_mask", _vp), ("rand", _vp)]
 
 
+class Weed(C.Structure):                  # include/gsrast.h gsr_octree_weed
+    _fields_ = [("cam_infos", _vp), ("C", C.c_int32), ("levels", C.c_int32), ("mode", C.c_int32), ("lv", C.c_int32),
+                ("standard_dist", C.c_float), ("fork", C.c_float), ("visible_threshold", C.c_float)]
+
+
+WEED_MODES = {"floor": 0, "round": 1, "ceil": 2}
+WEED_CHUNK = 256                          # include/gsrast.h GSR_OCTREE_WEED_CHUNK
+
+
+def make_weed(cam_infos, standard_dist, fork, levels, dist2level, visible_threshold, lv=0):
+    """(gsr_octree_weed, the camera tensor it points to) for cam_infos [C,4] (centre, scale) on the device; `lv` is the level of a growing pass."""
+    if dist2level == "progressive":
+        raise RuntimeError("dist2level 'progressive' is not supported by the weed-out: the reference's own weed_out cannot run in that mode")
+    if dist2level not in WEED_MODES:
+        raise RuntimeError(f"Unknown dist2level: {dist2level}")
+    cams = _f32(cam_infos, "cam_infos", (None, 4))
+    if cams.shape[0] < 1:
+        raise RuntimeError("cam_infos: expected at least one camera")
+    if int(levels) < 1:
+        raise RuntimeError(f"levels: expected a positive number but found {levels}")
+    return Weed(cams.data_ptr(), cams.shape[0], int(levels), WEED_MODES[dist2level], int(lv), float(standard_dist), float(fork), float(visible_threshold)), cams
+
+
 class RowsTensor(C.Structure):            # include/gsrast.h gsr_rows_tensor
     _fields_ = [("src", _vp), ("dst", _vp), ("tail", _vp), ("row_bytes", C.c_int64), ("n_tail", C.c_int64)]
 
@@ -46,6 +69,8 @@ def _lib():
                 ("gsr_anchor_level_scratch_bytes", sz, [C.c_int32] * 3),
                 ("gsr_anchor_level_find", C.c_int, [C.POINTER(Level), _vp, sz, _vp, _vp]),
                 ("gsr_anchor_level_emit", C.c_int, [C.POINTER(Level), _vp, sz, C.c_uint32, _vp, _vp, _vp]),
+                ("gsr_anchor_level_find_weed", C.c_int, [C.POINTER(Level), _vp, C.POINTER(Weed), _vp, sz, _vp, _vp]),
+                ("gsr_octree_weed_out", C.c_int, [_vp, _vp, C.c_int64, C.POINTER(Weed), _vp, _vp, _vp]),
                 ("gsr_rows_compact_scratch_bytes", sz, [C.c_int64]),
                 ("gsr_rows_compact_multi", C.c_int, [C.c_int64, _vp, C.c_int32, C.POINTER(RowsTensor), _vp, sz, _vp]),
                 ("gsr_densify_plan_scratch_bytes", sz, [C.c_int32, C.c_int32]),

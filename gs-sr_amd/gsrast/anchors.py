@@ -1,4 +1,5 @@
-"""Anchor growing and pruning of the Scaffold-GS models on the device (include/gsrast.h gsr_anchor_level_*, gsr_rows_compact_multi).
+"""Anchor growing and pruning of the Scaffold-GS and Octree-GS models on the device (include/gsrast.h gsr_anchor_level_*, gsr_octree_weed,
+gsr_rows_compact_multi).
 
 `adjust_anchor_(model)` replaces `ScaffoldGaussian.adjust_anchor` (gssr/gaussian/scaffold_gaussian.py:651-705) and the `anchor_growing` it calls
 (:555-649): the consumer of the statistics `gsrast.decode.training_stats_` accumulates.  The reference compares every unique candidate cell with
@@ -7,6 +8,12 @@ with a `nonzero()` host synchronisation; here a level is one sort over packed ce
 accumulator is one launch.  Results equal the reference's bit for bit (tests/test_gpu_anchor.py against fixtures its own code produced), with the
 two deviations of DESIGN.md §7: cells must fit 21 bits per axis, and the division by the cell size is a true division.
 
+`octree_adjust_anchor_(model, iteration)` does the same for `OctreeGaussian.adjust_anchor` (gssr/gaussian/octree_gaussian.py:536-588, with
+anchor_growing :401-534, weed_out :203-214 and get_remove_duplicates :374-385): per level two sorts in the place of two torch.unique calls and two
+all-pairs comparisons, and the weed-out of the new anchors -- in the reference a Python loop over every training camera, twice per level -- runs
+inside the level's find pass, before its count is read.  Same two deviations; dist2level 'progressive' raises, as the reference's own weed_out
+cannot run in that mode (:198 compares [N] with [U]).
+
 There is no CPU fallback: host tensors raise."""
 import ctypes as C
 import math
@@ -14,21 +21,30 @@ import math
 import torch
 
 from . import check, ptr, stream_ptr
-from ._rows import Level, RowsTensor, _bytes, _f32, _lib, groups, install_, moments
+from ._rows import Level, RowsTensor, _bytes, _f32, _lib, groups, install_, make_weed, moments
 
 PARAM_ATTRS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
 _SKIP = ("mlp", "conv", "feat_base", "embedding")        # param groups the reference's optimizer surgery leaves alone
 
 
 def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell, thr_lo, thr_hi=math.inf, rand=None, rand_thr=0.0, mask=None,
-               origin=(0.0, 0.0, 0.0), n0=None):
-    """One growing level (gsr_anchor_level_find + gsr_anchor_level_emit) -> (new_anchor [U,3], new_feat [U,F]).
+               origin=(0.0, 0.0, 0.0), n0=None, occupy=None, weed=None):
+    """One growing level (gsr_anchor_level_find + gsr_anchor_level_emit) -> (new_anchor [U,3], new_feat [U,F]); see _grow_level."""
+    return _grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, cell=cell, thr_lo=thr_lo, thr_hi=thr_hi, rand=rand, rand_thr=rand_thr,
+                       mask=mask, origin=origin, n0=n0, occupy=occupy, weed=weed)[:2]
+
+
+def _grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell, thr_lo, thr_hi=math.inf, rand=None, rand_thr=0.0, mask=None,
+                origin=(0.0, 0.0, 0.0), n0=None, occupy=None, weed=None):
+    """-> (new_anchor [U,3], new_feat [U,F], the number of new cells before the weed-out).
 
     anchor [Na,3]: the first n0 (default: all) own the candidate slots offset [n0,k,3] / grads [n0*k] / offset_mask [n0*k]; the others only occupy
     cells.  scaling [n0,>=3] is the ACTIVATED scaling, anchor_feat [n0,F].  Slot j is a candidate iff thr_lo <= grads[j] < thr_hi, offset_mask[j],
     rand[j] > rand_thr (rand given) and mask[j // k] (mask [n0] given; a masked-out original anchor does not occupy its cell either).  The new
     anchors are the distinct cells rint((anchor + offset * scaling - origin) / cell) of the candidates that hold no admitted anchor, in (x, y, z)
-    order, at cell * c + origin, with the element-wise maximum of the candidates' features.  One host synchronisation (the count)."""
+    order, at cell * c + origin, with the element-wise maximum of the candidates' features.  One host synchronisation (the count).
+    Octree-GS: occupy [n0] given, original anchor a occupies its cell iff occupy[a] and mask decides candidacy alone; weed (a gsr_octree_weed of
+    _rows.make_weed) given, the new positions are weighed against its cameras on the device and only the kept ones are counted and written."""
     anchor = _f32(anchor, "anchor", (None, 3))
     Na = anchor.shape[0]
     N0 = Na if n0 is None else int(n0)
@@ -53,6 +69,8 @@ def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell
             raise RuntimeError(f"rand: expected {N0 * k} entries but found {rand.numel()}")
     if mask is not None:
         mask = _bytes(mask, "mask", N0, anchor)
+    if occupy is not None:
+        occupy = _bytes(occupy, "occupy", N0, anchor)
     cell = float(cell)
     if not (cell > 0.0 and math.isfinite(cell)):
         raise RuntimeError(f"cell: expected a positive finite number but found {cell}")
@@ -71,9 +89,13 @@ def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell
     with torch.cuda.device(dev):
         nbytes = L.gsr_anchor_level_scratch_bytes(Na, N0, k)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        check(L.gsr_anchor_level_find(C.byref(lv), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)), "anchor_level_find")
-        count, overflow = status.tolist()                     # the level's one host synchronisation
+        status = torch.zeros(3, dtype=torch.int32, device=dev)
+        if occupy is None and weed is None:
+            check(L.gsr_anchor_level_find(C.byref(lv), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)), "anchor_level_find")
+        else:
+            check(L.gsr_anchor_level_find_weed(C.byref(lv), ptr(occupy), None if weed is None else C.byref(weed), ptr(scratch), nbytes, ptr(status),
+                                               stream_ptr(dev)), "anchor_level_find_weed")
+        count, overflow, found = status.tolist()              # the level's one host synchronisation
         if overflow:
             raise RuntimeError(f"gsrast anchor growing: a candidate cell lies outside the packing range of +-2^20 cells per axis "
                                f"(cell size {cell:g}: about +-{cell * (1 << 20):g} scene units around the origin)")
@@ -81,7 +103,7 @@ def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell
         new_feat = torch.empty(count, F, dtype=torch.float32, device=dev)
         if count:
             check(L.gsr_anchor_level_emit(C.byref(lv), ptr(scratch), nbytes, count, ptr(new_anchor), ptr(new_feat), stream_ptr(dev)), "anchor_level_emit")
-    return new_anchor, new_feat
+    return new_anchor, new_feat, (found if (occupy is not None or weed is not None) else count)
 
 
 def _host_log(x):
@@ -243,3 +265,154 @@ def adjust_anchor_(model, check_interval=100, success_threshold=0.8, grad_thresh
     Na = model._anchor.shape[0]
     model.max_radii2D = torch.zeros(Na, dtype=torch.float32, device=dev)
     return Na
+
+
+OCTREE_ATTRS = ("_level", "_extra_level", "levels", "fork", "voxel_size", "init_pos", "standard_dist", "cam_infos", "visible_threshold", "dist2level", "progressive",
+                "coarse_intervals")
+
+
+def _inverse_sigmoid_tenth():
+    xt = torch.full((16,), C.c_float(0.1).value, dtype=torch.float32)                      # inverse_sigmoid(0.1 * ones) in float32
+    return float(torch.log(xt / (1 - xt))[0])
+
+
+@torch.no_grad()
+def octree_adjust_anchor_(model, iteration, check_interval=100, success_threshold=0.8, grad_threshold=0.0002, update_ratio=0.5, extra_ratio=4.0, extra_up=0.25,
+                          min_opacity=0.005, trace=None):
+    """OctreeGaussian.adjust_anchor on the device, for any object with the Scaffold attributes adjust_anchor_ checks (without the update_* factors and
+    max_radii2D) and _level [N,1], _extra_level [N], levels, fork, voxel_size, init_pos, standard_dist, cam_infos [C,4], visible_threshold,
+    dist2level, progressive, coarse_intervals.  Per level l that holds anchors: pass A (slots of level-l anchors with cur_thr <= g < ds_thr, cells of
+    voxel_size / fork^l, occupied by every current level-l anchor, weeded with lv = l, feature = maximum) and, where the finer levels grow and level
+    l+1 holds anchors, pass B (g >= ds_thr, cells of a fork-th of that, occupied by the level-(l+1) anchors, weeded with lv = l+1, feature zeros).
+    Then one prune + append over parameters, Adam moments, accumulators, _level and _extra_level.  Host reads: the level histogram (with the
+    model's scalars where they live on the device), one count per pass that runs, the number of kept rows.  `trace`: a list that receives
+    (level, "A" | "B", cells found, cells kept) per pass.  Returns the number of anchors."""
+    for name in list(PARAM_ATTRS.values()) + ["get_scaling", "optimizer", "opacity_accum", "anchor_demon", "offset_gradient_accum", "offset_denom", "n_offsets"] + \
+            list(OCTREE_ATTRS):
+        if not hasattr(model, name):
+            raise RuntimeError(f"model: attribute {name} is missing")
+    if model.dist2level == "progressive":
+        raise RuntimeError("octree_adjust_anchor_: dist2level 'progressive' is not supported: the reference's own weed_out cannot run in that mode")
+    k = int(model.n_offsets)
+    anchor = _f32(model._anchor, "model._anchor", (None, 3))
+    N0 = anchor.shape[0]
+    dev = anchor.device
+    shapes = {"_offset": (N0, k, 3), "_anchor_feat": (N0, None), "_opacity": (N0, 1), "_scaling": (N0, 6), "_rotation": (N0, 4), "_extra_level": (N0,),
+              "opacity_accum": (N0, 1), "anchor_demon": (N0, 1), "offset_gradient_accum": (N0 * k, 1), "offset_denom": (N0 * k, 1)}
+    for name, shp in shapes.items():
+        _f32(getattr(model, name), "model." + name, shp)
+    level = model._level
+    if not isinstance(level, torch.Tensor) or level.device != dev or tuple(level.shape) != (N0, 1) or level.dtype not in (torch.int32, torch.float32):
+        raise RuntimeError(f"model._level: expected an int32 or float32 tensor of shape [{N0}, 1] on the device of model._anchor")
+    scaling = model.get_scaling() if callable(model.get_scaling) else model.get_scaling
+    scaling = _f32(scaling, "model.get_scaling", (N0, None))
+    F = model._anchor_feat.shape[1]
+    grp = groups(model, PARAM_ATTRS, _SKIP)
+    levels, fork = int(model.levels), model.fork
+    lvl = level.reshape(-1)
+
+    # the one read before the loop: anchors per level, and the model's scalars where they are device tensors (as create_from_data leaves them)
+    hist_dev = (lvl.reshape(-1, 1) == torch.arange(levels, device=dev, dtype=lvl.dtype)).sum(dim=0).to(torch.float64)
+    sizes = {"voxel_size": 1, "standard_dist": 1, "visible_threshold": 1, "init_pos": 3}
+    vals = {n: getattr(model, n) for n in sizes}
+    for n, v in vals.items():
+        if (v.numel() if isinstance(v, torch.Tensor) else len(v) if n == "init_pos" else 1) != sizes[n]:
+            raise RuntimeError(f"model.{n}: expected {sizes[n]} number(s)")
+    on_dev = [n for n in sizes if isinstance(vals[n], torch.Tensor) and vals[n].is_cuda]
+    host = torch.cat([hist_dev] + [vals[n].detach().to(dev, torch.float64).reshape(-1) for n in on_dev]).tolist()
+    hist, p = [int(c) for c in host[:levels]] + [0], levels
+    for n in on_dev:
+        vals[n] = host[p:p + sizes[n]]; p += sizes[n]
+    flat = lambda v: [float(x) for x in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v if isinstance(v, (list, tuple)) else [v])]
+    vs, standard_dist, visible_threshold = (C.c_float(flat(vals[n])[0]).value for n in ("voxel_size", "standard_dist", "visible_threshold"))
+    origin = flat(vals["init_pos"])
+    f32 = lambda x: C.c_float(x).value
+
+    # 1. statistics -> per-slot gradient, the slots seen often enough, per-anchor mean gradient (summed left to right)
+    grads = model.offset_gradient_accum / model.offset_denom
+    grads = torch.where(grads.isnan(), torch.zeros_like(grads), grads).abs().reshape(-1)
+    offset_mask = (model.offset_denom > check_interval * success_threshold * 0.5).reshape(-1)
+    grads = torch.where(offset_mask, grads, torch.zeros_like(grads))
+    g2, m2 = grads.reshape(N0, k), offset_mask.reshape(N0, k)
+    total = g2[:, 0].clone()
+    for j in range(1, k):
+        total += g2[:, j]
+    anchor_grads = total / (m2.sum(dim=1) + 1e-6)
+
+    # 2. the level loop
+    grow_ds = (not model.progressive) or iteration > model.coarse_intervals[-1]
+    update_value = fork ** update_ratio
+    rows = []                                                     # (positions, features, level, cell size) of every pass that added anchors
+    prev_b = None                                                 # the previous turn's pass-B anchors: the only appended ones of level l
+    for l in range(levels):
+        if hist[l] == 0:
+            prev_b = None
+            continue
+        cur_size = f32(vs / f32(float(fork) ** l))
+        ds_size = f32(cur_size / f32(fork))
+        cur_thr = grad_threshold * (update_value ** l)
+        ds_thr = cur_thr * update_value
+        if grow_ds:
+            model._extra_level[:N0] += extra_up * (anchor_grads >= cur_thr * extra_ratio).float()
+        is_l = lvl == l
+        cur = torch.cat((anchor, prev_b)) if prev_b is not None else anchor
+        w, cams = make_weed(model.cam_infos, standard_dist, fork, levels, model.dist2level, visible_threshold, lv=l)
+        a, f, found = _grow_level(cur, model._offset, scaling, model._anchor_feat, grads, offset_mask, cell=cur_size, thr_lo=cur_thr, thr_hi=ds_thr, mask=is_l,
+                                  occupy=is_l, origin=origin, n0=N0, weed=w)
+        if trace is not None:
+            trace.append((l, "A", found, a.shape[0]))
+        if a.shape[0]:
+            rows.append((a, f, l, cur_size)); hist[l] += a.shape[0]
+        prev_b = None
+        if grow_ds and l < levels - 1 and hist[l + 1] > 0:
+            w, cams = make_weed(model.cam_infos, standard_dist, fork, levels, model.dist2level, visible_threshold, lv=l + 1)
+            b, _, found = _grow_level(anchor, model._offset, scaling, model._anchor_feat[:, :0], grads, offset_mask, cell=ds_size, thr_lo=ds_thr, mask=is_l,
+                                      occupy=lvl == l + 1, origin=origin, weed=w)
+            if trace is not None:
+                trace.append((l, "B", found, b.shape[0]))
+            if b.shape[0]:
+                rows.append((b, torch.zeros(b.shape[0], F, dtype=torch.float32, device=dev), l + 1, ds_size)); hist[l + 1] += b.shape[0]
+                prev_b = b
+    U = sum(r[0].shape[0] for r in rows)
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    new_scaling, new_level = z(U, 6), z(U, 1)
+    p = 0
+    for a, _, l, size in rows:
+        new_scaling[p:p + a.shape[0]] = _host_log(size)
+        new_level[p:p + a.shape[0]] = float(l)
+        p += a.shape[0]
+    new_rotation = z(U, 4)
+    new_rotation[:, 0] = 1.0
+    d = {"anchor": torch.cat([r[0] for r in rows]) if rows else z(0, 3), "scaling": new_scaling, "rotation": new_rotation,
+         "anchor_feat": torch.cat([r[1] for r in rows]) if rows else z(0, F), "offset": z(U, k, 3),
+         "opacity": torch.full((U, 1), _inverse_sigmoid_tenth(), dtype=torch.float32, device=dev)}
+
+    # 3. reset the consumed statistics, prune mask
+    om = offset_mask.reshape(-1, 1)
+    model.offset_denom.masked_fill_(om, 0.0)
+    model.offset_gradient_accum.masked_fill_(om, 0.0)
+    anchors_mask = model.anchor_demon > check_interval * success_threshold
+    prune = (model.opacity_accum < min_opacity * model.anchor_demon) & anchors_mask
+    model.opacity_accum.masked_fill_(anchors_mask, 0.0)
+    model.anchor_demon.masked_fill_(anchors_mask, 0.0)
+    keep = ~prune.reshape(-1)
+    # 4. one compaction + append pass: [old[keep] ; new]
+    tensors, tails, carried = [], [], {}
+    for n, g in grp.items():
+        q = g["params"][0]
+        carried[n] = moments(model.optimizer, q)
+        tensors += [q] + list(carried[n] or ()); tails += [d[n]] + [U] * (2 if carried[n] else 0)
+    accs = ("opacity_accum", "anchor_demon", "offset_gradient_accum", "offset_denom")
+    tensors += [getattr(model, n) for n in accs[:2]] + [getattr(model, n).reshape(N0, k) for n in accs[2:]]
+    tails += [U] * 4
+    tensors += [level.to(torch.float32) if U else level, model._extra_level]          # torch.cat's promotion: float32 once anything was added
+    tails += [new_level if U else 0, U]
+    outs = iter(rows_compact(keep, tensors, tails))
+    for n, g in grp.items():
+        data = next(outs)
+        install_(model, g, PARAM_ATTRS[n], data, (next(outs), next(outs)) if carried[n] else None)
+    for n in accs:
+        setattr(model, n, next(outs).reshape(-1, 1))
+    model._level = next(outs)
+    model._extra_level = next(outs)
+    return model._anchor.shape[0]

@@ -1,7 +1,9 @@
 """Octree-GS level-of-detail mask fused with the visibility prefilter (include/gsrast.h gsr_octree_visible).
 
 Replaces `OctreeGaussianModel.set_anchor_mask` (gssr/gaussian/octree_gaussian.py:255-267, incl. map_to_int_level :184-203) followed by
-`OctreeScene.prefilter_voxel` (gssr/scene/octree_scene.py:136-172): no boolean-index gathers, no host synchronisation."""
+`OctreeScene.prefilter_voxel` (gssr/scene/octree_scene.py:136-172): no boolean-index gathers, no host synchronisation.
+
+`weed_out` is `OctreeGaussianModel.weed_out` (:203-214) over the kernel the anchor growing weighs its new anchors with (gsr_octree_weed_out)."""
 import ctypes as C
 
 import torch
@@ -39,3 +41,24 @@ def octree_visible(raster_settings, anchor, level, scaling, rotation, voxel_size
                                            ptr(radii), ptr(prog), ptr(trans), stream_ptr(dev)), "octree_visible")
         return {"anchor_mask": amask.view(torch.bool), "visible_mask": radii > 0, "radii": radii, "prog_ratio": prog,
                 "transition_mask": None if trans is None else trans.view(torch.bool)}
+
+
+def weed_out(positions, levels_of, cam_infos, standard_dist, fork, levels, dist2level="round", visible_threshold=0.0):
+    """-> (visible_count int32 [U], keep bool [U]): per position [U,3] of level levels_of [U] the number of cameras cam_infos [C,4] (centre, scale)
+    whose distance level admits it, and visible_count / C > visible_threshold.  The reference loops over the cameras with eight launches each;
+    this is one launch and no host synchronisation.  dist2level 'progressive' raises, as the reference's weed_out cannot run in it."""
+    from ._rows import _f32, _lib, make_weed
+    with torch.no_grad():
+        pos = _f32(positions, "positions", (None, 3))
+        U = pos.shape[0]
+        if not isinstance(levels_of, torch.Tensor) or levels_of.device != pos.device or levels_of.numel() != U:
+            raise RuntimeError(f"levels_of: expected a tensor of {U} entries on the device of positions")
+        lv = levels_of.reshape(-1).to(torch.int32).contiguous()
+        w, cams = make_weed(cam_infos, standard_dist, fork, levels, dist2level, visible_threshold)
+        if cams.device != pos.device:
+            raise RuntimeError("cam_infos must be on the device of positions")
+        count = torch.empty(U, dtype=torch.int32, device=pos.device)
+        keep = torch.empty(U, dtype=torch.uint8, device=pos.device)
+        with torch.cuda.device(pos.device):
+            check(_lib().gsr_octree_weed_out(ptr(pos), ptr(lv), U, C.byref(w), ptr(count), ptr(keep), stream_ptr(pos.device)), "octree_weed_out")
+        return count, keep.view(torch.bool)

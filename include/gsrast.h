@@ -463,6 +463,31 @@ size_t gsr_anchor_level_scratch_bytes(int32_t Na, int32_t N0, int32_t k);
 int gsr_anchor_level_find(const gsr_anchor_level* lv, void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[2]*/, void* stream);
 int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scratch, size_t scratch_bytes, uint32_t count, float* new_anchor /*[count,3]*/,
                           float* new_feat /*[count,F]*/, void* stream);
+/* Octree-GS (OctreeGaussian.anchor_growing / weed_out, octree_gaussian.py:401-534, :203-214; additions, no ABI bump).
+ * gsr_octree_weed: the cameras a new anchor is weighed against.  For a position p and a level lv, per camera (centre c, scale s), in float32
+ * with every operation rounded on its own:
+ *   d = sqrt(((p.x-c.x)^2 + (p.y-c.y)^2) + (p.z-c.z)^2) * s;  pred = log2(standard_dist / d) / (float)log2(fork)   (IEEE divisions)
+ *   il = clamp(floor | rint (half to even) | ceil (pred), 0, levels - 1), clamped in float before the conversion
+ *   visible = #cameras with lv <= il;  keep iff (float)visible / (float)C > visible_threshold.       d == 0 is outside the contract.
+ * mode: 0 floor, 1 round, 2 ceil; 3 ('progressive') is an error, as the reference's own weed_out cannot run in it (:198).
+ * gsr_anchor_level_find_weed is gsr_anchor_level_find with two additions; scratch, emit and the order of the result are the same.
+ *   occupy [N0] bytes or NULL: where given, original anchor a occupies its cell iff occupy[a] while its slots are candidates iff mask[a]
+ *     (pass B of an Octree level: candidates from level l, occupiers of level l+1); NULL: the mask decides both.  Anchors >= N0 always occupy.
+ *   weed or NULL: where given, every new position is weighed with lv = weed->lv before the count is published; gsr_anchor_level_emit then
+ *     writes the kept rows only.  status_dev has THREE words: {count, sticky overflow, count before the weed-out}.
+ * gsr_octree_weed_out: the same function over rows (positions [U,3], levels [U]; weed->lv is not read) -> visible_count [U], keep [U]. */
+#define GSR_OCTREE_WEED_CHUNK 256     /* cameras staged in LDS at a time */
+typedef struct gsr_octree_weed {
+    const float* cam_infos;           /* [C,4]: centre, scale */
+    int32_t C, levels;
+    int32_t mode;                     /* dist2level: 0 floor, 1 round, 2 ceil */
+    int32_t lv;                       /* the level of every new anchor of the pass */
+    float standard_dist, fork, visible_threshold;
+} gsr_octree_weed;
+int gsr_anchor_level_find_weed(const gsr_anchor_level* lv, const uint8_t* occupy /*[N0] or NULL*/, const gsr_octree_weed* weed /*or NULL*/, void* scratch,
+                               size_t scratch_bytes, uint32_t* status_dev /*[3]*/, void* stream);
+int gsr_octree_weed_out(const float* positions /*[U,3]*/, const int32_t* levels /*[U]*/, int64_t U, const gsr_octree_weed* weed,
+                        int32_t* visible_count /*[U]*/, uint8_t* keep /*[U]*/, void* stream);
 /* Row compaction + append for `count` tensors that share one keep mask over N rows, in one copy launch per 24 tensors (in the manner of
  * gsr_adam_step_multi): dst = [src[keep] ; tail], tail == NULL meaning n_tail rows of zeros.  Replaces the reference's per-tensor x[mask] + cat
  * (_prune_anchor_optimizer / cat_tensors_to_optimizer, scaffold_gaussian.py:460-541) over parameters, Adam moments and accumulators; the
