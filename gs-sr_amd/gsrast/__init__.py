@@ -67,7 +67,8 @@ class LodCfg(C.Structure):
 
 EXPORTS = ["gsr_geom_bytes", "gsr_img_bytes", "gsr_binning_bytes", "gsr_backward_scratch_bytes",
            "gsr_forward_stage1", "gsr_forward_stage2", "gsr_forward_stage1_ex", "gsr_forward_stage2_ex", "gsr_backward", "gsr_backward_ex", "gsr_forward_async", "gsr_mark_visible", "gsr_visible_filter",
-           "gsr_tsdf_integrate", "gsr_tsdf_integrate_dense", "gsr_tsdf_sparse_integrate2", "gsr_tsdf_sparse_status", "gsr_tsdf_sparse_rehash", "gsr_tsdf_sparse_merge", "gsr_tsdf_sparse_merge_volume", "gsr_tsdf_sparse_materialize", "gsr_loss_l1_linear", "gsr_dist2_scratch_bytes", "gsr_dist2", "gsr_debug_read", "gsr_last_error",
+           "gsr_tsdf_integrate", "gsr_tsdf_integrate_dense", "gsr_tsdf_sparse_integrate2", "gsr_tsdf_sparse_status", "gsr_tsdf_sparse_rehash", "gsr_tsdf_sparse_merge", "gsr_tsdf_sparse_merge_volume", "gsr_tsdf_sparse_materialize", "gsr_tsdf_sparse_mesh_scratch_bytes", "gsr_tsdf_sparse_mesh_count", "gsr_tsdf_sparse_mesh_emit",
+           "gsr_loss_l1_linear", "gsr_dist2_scratch_bytes", "gsr_dist2", "gsr_debug_read", "gsr_last_error",
            "gsr_abi_version", "gsr_profile_enable", "gsr_profile_read", "gsr_binning_capacity", "gsr_forward",
            "gsr_loss_l1_ssim_scratch_bytes", "gsr_loss_l1_ssim", "gsr_loss_surfel_geo_scratch_bytes", "gsr_loss_surfel_geo", "gsr_loss_plane_geo", "gsr_loss_scaling_prod", "gsr_octree_visible",
            "gsr_loss_plane_mv_scratch_bytes", "gsr_loss_plane_mv_geo", "gsr_loss_plane_mv_ncc", "gsr_loss_plane_mv_values", "gsr_loss_plane_mv_scale",
@@ -137,6 +138,11 @@ def lib():
     L.gsr_tsdf_sparse_merge_volume.argtypes = [C.POINTER(TsdfSparse), C.POINTER(TsdfSparse), C.c_int32, _vp]
     L.gsr_tsdf_sparse_materialize.restype = C.c_int
     L.gsr_tsdf_sparse_materialize.argtypes = [C.POINTER(TsdfSparse), C.c_int32, _vp]
+    L.gsr_tsdf_sparse_mesh_scratch_bytes.restype = sz; L.gsr_tsdf_sparse_mesh_scratch_bytes.argtypes = [C.c_int32]
+    L.gsr_tsdf_sparse_mesh_count.restype = C.c_int
+    L.gsr_tsdf_sparse_mesh_count.argtypes = [C.POINTER(TsdfSparse), C.c_int32, _vp, C.c_float, _vp, sz, C.POINTER(C.c_uint64), _vp]
+    L.gsr_tsdf_sparse_mesh_emit.restype = C.c_int
+    L.gsr_tsdf_sparse_mesh_emit.argtypes = [C.POINTER(TsdfSparse), C.c_int32, _vp, C.c_float, _vp, sz, _vp, _vp, _vp, _vp]
     L.gsr_adam_step_multi.restype = C.c_int
     L.gsr_adam_step_multi.argtypes = [C.c_int32, _vp, _vp]
     L.gsr_adam_step_multi_dev.restype = C.c_int

@@ -150,3 +150,72 @@ def load_anchors(path, device="cpu"):
         out["extra_level"] = t(a[:, col["extra_level"]])
         out["voxel_size"] = float(a[0, col["info"]]); out["standard_dist"] = float(a[1, col["info"]])
     return out
+
+
+def write_triangle_mesh(path, mesh):
+    """The mesh file `o3d.io.write_triangle_mesh` leaves for the reference (extract_mesh.py:130-135): binary little-endian PLY, element `vertex` with
+    x, y, z float and red, green, blue uchar, element `face` with `vertex_indices` as list uchar int.  mesh: anything with vertices [V,3],
+    vertex_colors [V,3] in [0,1] and triangles [T,3] (gsrast.tsdf.TriangleMesh, on any device)."""
+    v = np.asarray(mesh.vertices.detach().cpu(), dtype="<f4").reshape(-1, 3)
+    c = np.asarray(mesh.vertex_colors.detach().cpu(), dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(mesh.triangles.detach().cpu(), dtype="<i4").reshape(-1, 3)
+    if c.shape != v.shape:
+        raise ValueError(f"gsrast.ply: {c.shape[0]} colours for {v.shape[0]} vertices")
+    vert = np.empty(v.shape[0], dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    c8 = np.clip(np.rint(np.nan_to_num(c) * 255.0), 0, 255).astype(np.uint8)
+    vert["red"], vert["green"], vert["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    face = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"] = 3
+    face["i"] = t
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z",
+            "property uchar red", "property uchar green", "property uchar blue", f"element face {t.shape[0]}",
+            "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
+
+
+def read_triangle_mesh(path, device="cpu"):
+    """-> gsrast.tsdf.TriangleMesh of a binary little-endian PLY file with a `vertex` element (x, y, z and, optionally, red, green, blue; further
+    scalar properties are skipped) followed by a `face` element whose only property is a list of three indices per face."""
+    from .tsdf import TriangleMesh
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"gsrast.ply: {path} is not a PLY file")
+        fmt, elems = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("gsrast.ply: end of file inside the header")
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elems.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elems[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or [e[0] for e in elems] != ["vertex", "face"]:
+            raise ValueError("gsrast.ply: a triangle mesh is a binary_little_endian file with the elements vertex and face")
+        (_, nv, vp), (_, nf, fp) = elems
+        if any(p[0] == "list" for p in vp) or len(fp) != 1 or fp[0][0] != "list":
+            raise ValueError("gsrast.ply: vertex properties must be scalars and face must hold one list property")
+        vdt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in vp])
+        vert = np.frombuffer(f.read(vdt.itemsize * nv), dtype=vdt, count=nv)
+        fdt = np.dtype([("n", "<" + _PLY_TYPES[fp[0][1]]), ("i", "<" + _PLY_TYPES[fp[0][2]], (3,))])
+        face = np.frombuffer(f.read(fdt.itemsize * nf), dtype=fdt, count=nf)
+        if nf and not (face["n"] == 3).all():
+            raise ValueError("gsrast.ply: faces other than triangles")
+    xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    if "red" in vdt.names and nv:
+        col = np.stack([vert["red"], vert["green"], vert["blue"]], axis=1).astype(np.float32) / np.float32(255.0)
+    else:
+        col = np.zeros((nv, 3), np.float32)
+    tri = face["i"].astype(np.int32).reshape(nf, 3)
+    t = lambda a, dt: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=device)
+    return TriangleMesh(t(xyz, torch.float32), t(col, torch.float32), t(tri, torch.int32))

@@ -97,6 +97,21 @@ def brick_to_xmajor(planes):
     return v.permute(*range(k), k + 0, k + 3, k + 5, k + 1, k + 4, k + 6, k + 2, k + 7).reshape(lead + (16, 16, 16))
 
 
+class TriangleMesh:
+    """What `ScalableTSDFVolume.extract_triangle_mesh()` returns -- the three arrays of Open3D's `TriangleMesh` the reference goes on to use
+    (extract_mesh.py:130-135 writes them to a PLY file): vertices [V,3] float32, vertex_colors [V,3] float32 in [0,1], triangles [T,3] int32,
+    on the volume's device."""
+
+    def __init__(self, vertices, vertex_colors, triangles):
+        self.vertices, self.vertex_colors, self.triangles = vertices, vertex_colors, triangles
+
+    def cpu(self):
+        return TriangleMesh(self.vertices.cpu(), self.vertex_colors.cpu(), self.triangles.cpu())
+
+    def __repr__(self):
+        return f"TriangleMesh({int(self.vertices.shape[0])} vertices, {int(self.triangles.shape[0])} triangles, {self.vertices.device})"
+
+
 class ScalableTSDFVolume:
     """Block-sparse TSDF volume with the call shape of o3d.pipelines.integration.ScalableTSDFVolume as GS-SR drives it
     (gssr/utils/mesh_utils.py:154-178: `ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8)`, `integrate(rgbd, intrinsic, extrinsic)` with
@@ -348,6 +363,46 @@ class ScalableTSDFVolume:
         # storage index bits, high to low: bx by bz (2 each) | x1 y1 x0 y0 | z (2)
         rec = brick_to_xmajor(self.records(n))                      # [n, 5, 16, 16, 16]
         return self.coord[:n], rec[:, 0], rec[:, 1], rec[:, 2:5].permute(0, 2, 3, 4, 1)
+
+    def _mesh_count(self, min_weight=0.0):
+        """First pass of the mesh extraction (gsr_tsdf_sparse_mesh_count): -> (n units, their output order, scratch, vertices, triangles)."""
+        import ctypes as C
+        n = self.num_units
+        if n == 0:
+            return 0, None, None, 0, 0
+        co = self.coord[:n].to(torch.int64) + (1 << 20)
+        order = torch.argsort((co[:, 0] << 42) | (co[:, 1] << 21) | co[:, 2]).to(torch.int32)      # ascending (x, y, z): the mesh does not depend on the pool layout
+        nbytes = int(lib().gsr_tsdf_sparse_mesh_scratch_bytes(n))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        counts = (C.c_uint64 * 2)()
+        st = self._struct()
+        with torch.cuda.device(self.device):
+            check(lib().gsr_tsdf_sparse_mesh_count(C.byref(st), n, ptr(order), float(min_weight), ptr(scratch), nbytes, counts, stream_ptr(self.device)),
+                  "tsdf_sparse_mesh_count")
+        return n, order, scratch, int(counts[0]), int(counts[1])
+
+    def _mesh_emit(self, n, order, scratch, V, T, min_weight=0.0):
+        """Second pass (gsr_tsdf_sparse_mesh_emit) behind `_mesh_count` with the same min_weight."""
+        import ctypes as C
+        mesh = TriangleMesh(torch.empty((V, 3), dtype=torch.float32, device=self.device), torch.empty((V, 3), dtype=torch.float32, device=self.device),
+                            torch.empty((T, 3), dtype=torch.int32, device=self.device))
+        if V == 0 or T == 0:
+            return mesh
+        st = self._struct()
+        with torch.cuda.device(self.device):
+            check(lib().gsr_tsdf_sparse_mesh_emit(C.byref(st), n, ptr(order), float(min_weight), ptr(scratch), int(scratch.numel()), ptr(mesh.vertices),
+                                                  ptr(mesh.vertex_colors), ptr(mesh.triangles), stream_ptr(self.device)), "tsdf_sparse_mesh_emit")
+        return mesh
+
+    def extract_triangle_mesh(self, min_weight=0.0):
+        """-> TriangleMesh: marching cubes over the voxels whose weight exceeds `min_weight` (0: Open3D's rule `w != 0`), the call the reference ends its
+        fusion loop with (gssr/utils/mesh_utils.py:178).  Frames still in flight are waited for.  The mesh comes out of the pools where they lie -- the
+        volume is neither materialised nor copied, and it is left bit for bit as it was; scratch is about 2 KB per unit.  Vertices, colours and triangles
+        are a pure function of the volume's content (include/gsrast.h, gsr_tsdf_sparse_mesh_count): units in ascending coordinate order, voxels x-major,
+        so volumes with equal content give byte-identical meshes whatever their insertion order, capacity or chunking."""
+        self.finish()
+        n, order, scratch, V, T = self._mesh_count(min_weight)
+        return self._mesh_emit(n, order, scratch, V, T, min_weight)
 
     def merge_units_(self, coords, tsdf, weight, color, assume_unique=False):
         """self <- weighted merge with the given units (plain arrays shaped like `units()`, on this device).  The merge kernel runs one workgroup per

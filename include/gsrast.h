@@ -260,6 +260,28 @@ int gsr_tsdf_sparse_merge(const gsr_tsdf_sparse* vol, int32_t n_units, const int
 int gsr_tsdf_sparse_merge_volume(const gsr_tsdf_sparse* vol, const gsr_tsdf_sparse* other, int32_t n_units, void* stream);
 /* ABI 8.  Zero-fills the never-written groups of units [0, n_units) and marks them written: afterwards the pools are plain arrays (still in brick order). */
 int gsr_tsdf_sparse_materialize(const gsr_tsdf_sparse* vol, int32_t n_units, void* stream);
+/* The triangle mesh of the volume (the role of `volume.extract_triangle_mesh()`, gssr/utils/mesh_utils.py:178; extends ABI 8), read from the pools where
+ * they lie: the volume is not materialised and not written.  The mesh, defined:
+ *  - a voxel COUNTS iff its weight > min_weight (0: Open3D's `w != 0`); a clear written-group bit, a unit with stamp 0 and a unit that is not in the table
+ *    read as weight 0.  Voxel (x,y,z) of the unit at `coord` has the global index G = 16*coord + (x,y,z) and the centre voxel_length*(G + 0.5).
+ *  - the cube with origin G has corner i at G + (i&1, (i>>1)&1, (i>>2)&1); it is VALID iff its 8 corners count; its case has bit i set iff tsdf_i < 0
+ *    (a tsdf of exactly 0 is outside); the triangles of a case are those of csrc/gsr_mc_table.h (tools/gen_mc_table.py), cases 0 and 255 have none.
+ *  - the edge from G to G + e_a carries one vertex iff the signs of its ends differ and at least one of its four cubes is valid: no vertex is unreferenced,
+ *    none appears twice (also across units).  With f0 the tsdf at G, t = f0 / (f0 - f1): the position's component a is voxel_length*((float)G_a + 0.5f + t),
+ *    the other two voxel_length*((float)G + 0.5f) (float32, no FMA contraction); the colour (c0 + t*(c1 - c0)) / 255.  Triangles that are degenerate
+ *    because t is 0 or 1 are kept.
+ *  - order: units as `order` lists them (a permutation of [0, n_units): for a mesh that does not depend on the pool layout, ascending (coord.x, coord.y,
+ *    coord.z)); inside a unit voxels x-major with z fastest; inside a voxel vertices by axis 0, 1, 2 and triangles in table order.  The mesh is a pure
+ *    function of the volume's content and `order`.
+ * gsr_tsdf_sparse_mesh_count writes the per-unit state of the mesh into `scratch` (gsr_tsdf_sparse_mesh_scratch_bytes(n_units) bytes of device memory,
+ * 16-byte aligned, about 2 KB per unit) and returns the number of vertices and of triangles in counts_host[0 / 1] (HOST; it synchronises once); more
+ * than 2^31 - 1 of either is refused.  gsr_tsdf_sparse_mesh_emit, called with the same arguments and the scratch as count left it, writes
+ * vertices [V,3] float32, colors [V,3] float32 in [0,1] and triangles [T,3] int32 (device). */
+size_t gsr_tsdf_sparse_mesh_scratch_bytes(int32_t n_units);
+int gsr_tsdf_sparse_mesh_count(const gsr_tsdf_sparse* vol, int32_t n_units, const int32_t* order /*[n_units] device*/, float min_weight, void* scratch,
+                               size_t scratch_bytes, uint64_t* counts_host /*[2]*/, void* stream);
+int gsr_tsdf_sparse_mesh_emit(const gsr_tsdf_sparse* vol, int32_t n_units, const int32_t* order, float min_weight, void* scratch, size_t scratch_bytes,
+                              float* vertices, float* colors, int32_t* triangles, void* stream);
 /* Fused image-side loss right behind the rasterizer (the L1 term of gssr/scene/vanilla_scene.py:63-69
  * plus a linear functional of the auxiliary maps): loss = mean|color - gt| + sum(aux * waux); one streaming pass
  * writes dL/dcolor = sign(color-gt)/n and accumulates the scalar into *loss_out (device, caller zero-fills).
