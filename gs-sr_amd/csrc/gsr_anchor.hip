@@ -420,14 +420,24 @@ __global__ void __launch_bounds__(ANC_BLOCK) k_rows_count(const uint8_t* __restr
     block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
-__global__ void __launch_bounds__(ANC_BLOCK) k_rows_map(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ map)
+__global__ void __launch_bounds__(ANC_BLOCK) k_rows_map(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ map,
+                                                        uint32_t* __restrict__ rank)
 {
     __shared__ uint32_t lds[17];
     const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
     const bool f = i < N && keep[i];
     uint32_t tot;
     const uint32_t p = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);          // p <= i < N
-    if (f) map[p] = i;
+    if (f && map) map[p] = i;
+    if (f && rank) rank[i] = p;
+}
+// The keep scan on its own (gsr_common.h): block counts, k_scan_small, placement.  sums holds ceil(N / 1024) + 1 words.
+void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_t* map, uint32_t* rank, uint32_t* count_dev, hipStream_t s)
+{
+    const uint32_t nblk = gsr_div_up(N > 0 ? N : 1u, ANC_BLOCK);
+    hipLaunchKernelGGL(k_rows_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, N, sums);
+    gsr_scan_small(sums, nblk, 1, 0, count_dev, nullptr, s);
+    hipLaunchKernelGGL(k_rows_map, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, N, sums, map, rank);
 }
 
 struct RowsScratch { uint32_t *sums, *map, *count; size_t bytes; };
@@ -459,10 +469,7 @@ extern "C" int gsr_rows_compact_multi(int64_t N, const uint8_t* keep, int32_t co
     const gsr_rows_map m = {r.map, r.count, (uint32_t)N, 0u, (uint32_t)N};
     hipStream_t s = (hipStream_t)stream;
     if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, false, s)) return 1;                      // the checks, before anything is launched
-    const uint32_t nblk = gsr_div_up((uint32_t)(N > 0 ? N : 1), ANC_BLOCK);
-    hipLaunchKernelGGL(k_rows_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums);
-    gsr_scan_small(r.sums, nblk, 1, 0, r.count, nullptr, s);
-    hipLaunchKernelGGL(k_rows_map, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, (uint32_t)N, r.sums, r.map);
+    gsr_rows_keep_scan(keep, (uint32_t)N, r.sums, r.map, nullptr, r.count, s);
     if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, true, s)) return 1;
     return gsr_check_launch(who, s, false);
 }

@@ -181,3 +181,6 @@ struct gsr_rows_item { const void* src; void* dst; const void* tail; int64_t row
 struct gsr_rows_map { const uint32_t* map; const uint32_t* n_map_dev; uint32_t n_map, n_carried, src_rows; };
 // Checks the table (errors are prefixed with `who`), then launches unless !launch: an entry point with kernels of its own in front validates first.
 int gsr_rows_move(const char* who, const gsr_rows_map& m, int32_t count, const gsr_rows_item* t, bool launch, hipStream_t s);
+// The keep scan of the row compaction on its own (gsr_anchor.hip): for every i < N with keep[i], p = the number of kept rows in front of it;
+// map[p] = i and rank[i] = p (either may be NULL), *count_dev = the number kept.  Count / scan / place passes; sums: ceil(N / 1024) + 1 words.
+void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_t* map, uint32_t* rank, uint32_t* count_dev, hipStream_t s);

@@ -74,7 +74,8 @@ EXPORTS = ["gsr_geom_bytes", "gsr_img_bytes", "gsr_binning_bytes", "gsr_backward
            "gsr_loss_plane_mv_scratch_bytes", "gsr_loss_plane_mv_geo", "gsr_loss_plane_mv_ncc", "gsr_loss_plane_mv_values", "gsr_loss_plane_mv_scale",
            "gsr_plane_allmap", "gsr_plane_allmap_backward", "gsr_gauss_activations", "gsr_gauss_activations_backward", "gsr_sample_mask_scratch_bytes", "gsr_sample_mask", "gsr_densify_stats", "gsr_adam_step", "gsr_adam_step_multi", "gsr_adam_step_multi_dev",
            "gsr_anchor_level_scratch_bytes", "gsr_anchor_level_find", "gsr_anchor_level_emit", "gsr_anchor_level_find_weed", "gsr_octree_weed_out", "gsr_rows_compact_scratch_bytes", "gsr_rows_compact_multi",
-           "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_emit"]
+           "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_emit",
+           "gsr_mesh_post_scratch_bytes", "gsr_mesh_cluster_triangles", "gsr_mesh_filter_count", "gsr_mesh_filter_emit"]
 PROF_LABELS = ["preprocess", "depth_order", "binning", "blend_fwd", "bwd_memset", "blend_bwd", "preprocess_bwd", "_"]
 
 _lib = None
@@ -262,3 +263,6 @@ def make_cfg(variant, P, settings, D, M, render_geo, keep):
         keep.append(t)
         setattr(cfg, name, t.data_ptr())
     return cfg
+
+
+from .mesh import cluster_connected_triangles, post_process_mesh  # noqa: E402,F401  (gsrast.mesh needs the helpers above)

@@ -1,0 +1,157 @@
+"""Floaters filtered from an extracted mesh on the device: `post_process_mesh` of the reference (gssr/utils/mesh_utils.py:28-48, called by
+extract_mesh.py:130-134 and extract_mesh_split.py:122-127 on what `extract_triangle_mesh()` returned) and the Open3D call it starts with,
+`cluster_connected_triangles`.  Open3D is not part of the reference tree: PARITY UNPINNED (semantics restated from Open3D 0.18's published
+sources in include/gsrast.h, gsr_mesh_*; kernels in csrc/gsr_mesh_post.hip).  Every integer result is exact and a pure function of the index
+buffer; the cluster areas are added up with double atomics and are the one result that is not bit-reproducible.
+
+There is no CPU path: a mesh that is not on a HIP device raises, like ScalableTSDFVolume."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import check, lib, ptr, stream_ptr
+from ._rows import RowsTensor
+
+_vp = C.c_void_p
+DROP_UNREFERENCED, DROP_DEGENERATE = 1, 2             # include/gsrast.h GSR_MESH_DROP_*
+ERR_INDEX, ERR_INTERNAL, ERR_KEEP = 1, 2, 4           # GSR_MESH_ERR_*
+FLOOR = 50                                            # mesh_utils.py:41 "filter meshes smaller than 50"
+
+
+class Filter(C.Structure):                # include/gsrast.h gsr_mesh_filter
+    _fields_ = [("triangles", _vp), ("remove_mask", _vp), ("n_triangles", C.c_int64), ("n_vertices", C.c_int64), ("cluster_to_keep", C.c_int32),
+                ("floor", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = lib()
+    if not _bound:
+        sz = C.c_size_t
+        for name, res, args in (
+                ("gsr_mesh_post_scratch_bytes", sz, [C.c_int64, C.c_int64]),
+                ("gsr_mesh_cluster_triangles", C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, sz, _vp, _vp]),
+                ("gsr_mesh_filter_count", C.c_int, [C.POINTER(Filter), _vp, sz, _vp, _vp]),
+                ("gsr_mesh_filter_emit", C.c_int, [C.POINTER(Filter), _vp, sz, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(RowsTensor), _vp, _vp])):
+            f = getattr(L, name)
+            f.restype, f.argtypes = res, args
+        _bound = True
+    return L
+
+
+def _arrays(mesh):
+    """(vertices, vertex_colors, triangles) of a TriangleMesh, checked: contiguous float32 [V,3] x 2 and int32 [T,3] on one HIP device."""
+    v, c, t = mesh.vertices, mesh.vertex_colors, mesh.triangles
+    for x, name, dt in ((v, "vertices", torch.float32), (c, "vertex_colors", torch.float32), (t, "triangles", torch.int32)):
+        if not isinstance(x, torch.Tensor):
+            raise RuntimeError(f"mesh.{name} must be a tensor")
+        if not x.is_cuda:
+            raise RuntimeError(f"mesh.{name} must be a CUDA tensor: the mesh filter has no CPU path")
+        if x.dtype != dt or x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError(f"mesh.{name}: expected a {dt} tensor of shape [n, 3] but found {x.dtype} {list(x.shape)}")
+    if v.device != t.device or c.device != t.device:
+        raise RuntimeError("mesh: vertices, vertex_colors and triangles must be on one device")
+    if c.shape[0] != v.shape[0]:
+        raise RuntimeError(f"mesh.vertex_colors: expected {v.shape[0]} rows but found {c.shape[0]}")
+    return v.contiguous(), c.contiguous(), t.contiguous()
+
+
+def _scratch(T, V, dev):
+    n = int(_lib().gsr_mesh_post_scratch_bytes(T, V))
+    if n == 0:
+        raise RuntimeError(f"mesh: {T} triangles / {V} vertices: 3T must stay below 2^31 (the half-edges are indexed with 32 bits); filter the mesh in parts")
+    return torch.empty(n, dtype=torch.uint8, device=dev), n
+
+
+def _raise_status(status):
+    if status & ERR_INDEX:
+        raise RuntimeError("mesh: a triangle index lies outside [0, number of vertices)")
+    if status & ERR_INTERNAL:
+        raise RuntimeError("mesh: internal error, a bounded loop of the clustering ran out")
+
+
+def cluster_connected_triangles(mesh, with_area=True):
+    """-> (triangle_clusters int32 [T], cluster_n_triangles int32 [C], cluster_area float64 [C] or None), device tensors: Open3D's
+    `TriangleMesh.cluster_connected_triangles()`.  Two triangles are connected iff they share an undirected edge; clusters are numbered in
+    ascending order of their smallest triangle.  The integer results are exact; the areas are sums of double atomics, equal to the float64 sum
+    up to the order of the additions (not bit-reproducible).  One host read-back (the number of clusters)."""
+    v, _, t = _arrays(mesh)
+    T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
+    clusters = torch.empty(T, dtype=torch.int32, device=dev)
+    counts = torch.empty(T, dtype=torch.int32, device=dev)
+    area = torch.empty(T, dtype=torch.float64, device=dev) if with_area else None
+    scratch, nbytes = _scratch(T, 0, dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib().gsr_mesh_cluster_triangles(ptr(t), T, V, ptr(v) if with_area else None, ptr(clusters), ptr(counts), ptr(area), ptr(scratch), nbytes,
+                                                ptr(status), stream_ptr(dev)), "mesh_cluster_triangles")
+    st, n = status.tolist()
+    _raise_status(st)
+    return clusters, counts[:n].clone(), (area[:n].clone() if with_area else None)
+
+
+def _filter(mesh, remove_mask=None, cluster_to_keep=0, flags=0):
+    """One count call, the one host read-back, one emit call -> (vertices, vertex_colors, triangles, record); the mesh is only read.  Without
+    DROP_UNREFERENCED the vertex tensors are the mesh's own."""
+    v, c, t = _arrays(mesh)
+    T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
+    f = Filter(t.data_ptr() if T else None, None if remove_mask is None else remove_mask.data_ptr(), T, V, int(cluster_to_keep), FLOOR, int(flags), 0)
+    scratch, nbytes = _scratch(T, V, dev)
+    record = torch.empty(8, dtype=torch.int32, device=dev)
+    L = _lib()
+    with torch.cuda.device(dev):
+        check(L.gsr_mesh_filter_count(C.byref(f), ptr(scratch), nbytes, ptr(record), stream_ptr(dev)), "mesh_filter_count")
+        rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back
+        if rec[0] & ERR_KEEP and not rec[0] & (ERR_INDEX | ERR_INTERNAL):
+            raise IndexError(f"index -{cluster_to_keep} is out of bounds for axis 0 with size {rec[1]}")      # numpy's words for n[-cluster_to_keep]
+        _raise_status(rec[0])
+        n_v, n_t = rec[3], rec[4]
+        tris = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        rows, n_rows = None, 0
+        if flags & DROP_UNREFERENCED:
+            nv, nc = torch.empty((n_v, 3), dtype=torch.float32, device=dev), torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+            rows, n_rows = (RowsTensor * 2)(RowsTensor(v.data_ptr(), nv.data_ptr(), None, 12, 0), RowsTensor(c.data_ptr(), nc.data_ptr(), None, 12, 0)), 2
+        else:
+            nv, nc = v, c
+        check(L.gsr_mesh_filter_emit(C.byref(f), ptr(scratch), nbytes, (C.c_uint32 * 8)(*rec), n_rows, rows, ptr(tris) if n_t else None, stream_ptr(dev)),
+              "mesh_filter_emit")
+    return nv, nc, tris, rec
+
+
+def post_process_mesh(mesh, cluster_to_keep=1000):
+    """The reference's post_process_mesh (gssr/utils/mesh_utils.py:28-48) on the device -> a new TriangleMesh on the mesh's device; the input is
+    left untouched (the reference deep-copies it).
+      1. n = sort(cluster_n_triangles); threshold = max(n[-cluster_to_keep], 50)
+      2. triangles whose cluster has fewer triangles than the threshold go (strictly fewer: ties stay); the others keep their order
+      3. vertices no surviving triangle references go; order kept, colours move with their vertices bit for bit, triangle indices renumbered
+      4. triangles with two equal indices go, after step 3: a vertex only such a triangle references stays, as in the reference
+    cluster_to_keep larger than the number of clusters (an empty mesh included) raises IndexError, as numpy does in the reference;
+    cluster_to_keep < 1 raises ValueError -- a departure: there a negative index quietly selects from the other end, which means nothing.
+    Exactly ONE host read-back per call: the five-word record {status, clusters, threshold, vertices kept, triangles kept} between the
+    counting and the emitting pass.  Parity with Open3D unpinned (module docstring)."""
+    from .tsdf import TriangleMesh
+    if int(cluster_to_keep) != cluster_to_keep or cluster_to_keep < 1:
+        raise ValueError(f"cluster_to_keep must be a positive integer but found {cluster_to_keep}")
+    if cluster_to_keep > 0x7FFFFFFF:
+        _arrays(mesh)
+        raise IndexError(f"index -{cluster_to_keep} is out of bounds for axis 0")
+    v, c, t, _ = _filter(mesh, cluster_to_keep=int(cluster_to_keep), flags=DROP_UNREFERENCED | DROP_DEGENERATE)
+    return TriangleMesh(v, c, t)
+
+
+def as_remove_mask(mask, n, device):
+    """A numpy or torch bool (or uint8) mask of n triangles as bytes on `device`."""
+    if isinstance(mask, torch.Tensor):
+        m = mask
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"mask: expected a bool mask but found {m.dtype}")
+    if m.numel() != n:
+        raise RuntimeError(f"mask: expected {n} entries, one per triangle, but found {m.numel()}")
+    m = m.reshape(-1).to(device).contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m

@@ -108,6 +108,41 @@ class TriangleMesh:
     def cpu(self):
         return TriangleMesh(self.vertices.cpu(), self.vertex_colors.cpu(), self.triangles.cpu())
 
+    def clone(self):
+        return TriangleMesh(self.vertices.clone(), self.vertex_colors.clone(), self.triangles.clone())
+
+    def __deepcopy__(self, memo):
+        return self.clone()
+
+    # The four Open3D calls of the reference's post_process_mesh (gssr/utils/mesh_utils.py:33-45), under their names, so that its body runs against
+    # this class as it stands; gsrast.mesh.post_process_mesh is the same filter as one call with one host read-back.  No CPU path: a host mesh raises.
+    def cluster_connected_triangles(self):
+        """-> (triangle_clusters, cluster_n_triangles, cluster_area) as HOST numpy arrays, the way Open3D hands out host vectors the reference
+        wraps in np.asarray; gsrast.mesh.cluster_connected_triangles returns the device tensors."""
+        from . import mesh as _m
+        return tuple(x.cpu().numpy() for x in _m.cluster_connected_triangles(self))
+
+    def _filter_(self, **kw):
+        from . import mesh as _m
+        self.vertices, self.vertex_colors, self.triangles, _ = _m._filter(self, **kw)
+        return self
+
+    def remove_triangles_by_mask(self, mask):
+        """In place: triangle t goes where mask[t] (numpy or torch bool, one entry per triangle); vertices stay."""
+        from . import mesh as _m
+        _m._arrays(self)
+        return self._filter_(remove_mask=_m.as_remove_mask(mask, int(self.triangles.shape[0]), self.triangles.device))
+
+    def remove_unreferenced_vertices(self):
+        """In place: vertices no triangle references go, colours with them; order kept, indices renumbered."""
+        from . import mesh as _m
+        return self._filter_(flags=_m.DROP_UNREFERENCED)
+
+    def remove_degenerate_triangles(self):
+        """In place: triangles with two equal indices go; vertices stay."""
+        from . import mesh as _m
+        return self._filter_(flags=_m.DROP_DEGENERATE)
+
     def __repr__(self):
         return f"TriangleMesh({int(self.vertices.shape[0])} vertices, {int(self.triangles.shape[0])} triangles, {self.vertices.device})"
 

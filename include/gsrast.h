@@ -575,6 +575,47 @@ typedef struct gsr_densify_compute {
 } gsr_densify_compute;
 int gsr_densify_emit(const gsr_densify_args* a, const void* scratch, size_t scratch_bytes, const uint32_t* counts /*[8] host*/, int32_t count,
                      const gsr_densify_tensor* t, const gsr_densify_compute* c, void* stream);
+/* ---- floaters filtered from a triangle mesh (no ABI bump: additions only).
+ * The four Open3D calls of the reference's post_process_mesh (gssr/utils/mesh_utils.py:28-48): cluster_connected_triangles,
+ * remove_triangles_by_mask, remove_unreferenced_vertices, remove_degenerate_triangles.  Open3D is not part of the reference tree: the semantics
+ * below are restated from Open3D 0.18's published sources and their PARITY IS UNPINNED.  triangles: int32 [T,3], indices into V vertices.
+ *   adjacency: two triangles are adjacent iff they share an undirected edge (min(a,b), max(a,b)); a shared vertex alone does not connect, an edge
+ *     of three or more triangles connects all of them, a triangle equal to another is adjacent to it, and the (a,a) edge of an index-degenerate
+ *     triangle is an edge like any other.
+ *   clusters: the connected components, numbered 0..C-1 in ascending order of their smallest triangle index (Open3D's BFS order).
+ * gsr_mesh_cluster_triangles: triangle_clusters [T], cluster_n_triangles [T] of which the first C are written (the rest is zero), cluster_area
+ *   [T] doubles or NULL likewise: sum of 0.5 * |(v1 - v0) x (v2 - v0)| in double from the float32 vertices, added up with double atomics -- the
+ *   one output that is NOT bit-reproducible (the order of the additions varies from run to run); every integer output is exact.  vertices may be
+ *   NULL when cluster_area is: no vertex memory is touched then, whatever V says.  status_dev [2]: {status, C}.  scratch:
+ *   gsr_mesh_post_scratch_bytes(T, 0).
+ * status bits: GSR_MESH_ERR_INDEX an index outside [0, V) (such a triangle is never dereferenced; the results are to be discarded),
+ *   GSR_MESH_ERR_KEEP cluster_to_keep > C, GSR_MESH_ERR_INTERNAL a bounded loop ran out (cannot happen).  3T >= 2^31 is refused by every call.
+ * gsr_mesh_filter_count / _emit: the filter as one count call, one read of the record by the caller (its one host synchronisation) and one emit call.
+ *   1. keep rule -- remove_mask [T] bytes: triangle t goes iff remove_mask[t] != 0;  else cluster_to_keep = k > 0: with n the sorted cluster sizes and
+ *      thr = max(n[C - k], floor), triangle t goes iff the size of its cluster < thr (strictly: ties stay);  else every triangle stays.
+ *   2. GSR_MESH_DROP_UNREFERENCED: the vertices no triangle that survived step 1 references go, the others keep their order; the triangle indices are
+ *      renumbered and the rows of every tensor in `rows` (vertices, colours, ...; src / dst / row_bytes, bit for bit) move with them.
+ *   3. GSR_MESH_DROP_DEGENERATE: triangles with two equal indices go, AFTER step 2 (a vertex only such a triangle references stays).
+ *   Surviving triangles keep their order.  record_dev [8 words, 5 used]: {status, C, thr, V', T'} (C and thr 0 without the cluster rule).  The emit
+ *   takes the HOST copy of the record, refuses a non-zero status, and writes triangles_out [T',3] and the rows' dst [V', .]; `scratch`
+ *   (>= gsr_mesh_post_scratch_bytes(T, V), caller-owned) must stay unmodified between the two calls.  Inputs are only read. */
+enum { GSR_MESH_DROP_UNREFERENCED = 1, GSR_MESH_DROP_DEGENERATE = 2 };
+enum { GSR_MESH_ERR_INDEX = 1, GSR_MESH_ERR_INTERNAL = 2, GSR_MESH_ERR_KEEP = 4 };
+typedef struct gsr_mesh_filter {
+    const int32_t* triangles;         /* [T,3] */
+    const uint8_t* remove_mask;       /* [T] or NULL */
+    int64_t n_triangles, n_vertices;
+    int32_t cluster_to_keep;          /* 0: no cluster rule */
+    int32_t floor;                    /* 50 in the reference */
+    int32_t flags, pad_;
+} gsr_mesh_filter;
+size_t gsr_mesh_post_scratch_bytes(int64_t n_triangles, int64_t n_vertices);
+int gsr_mesh_cluster_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const float* vertices /*[V,3] or NULL*/,
+                               int32_t* triangle_clusters /*[T]*/, int32_t* cluster_n_triangles /*[T]*/, double* cluster_area /*[T] or NULL*/,
+                               void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[2]*/, void* stream);
+int gsr_mesh_filter_count(const gsr_mesh_filter* f, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[8]*/, void* stream);
+int gsr_mesh_filter_emit(const gsr_mesh_filter* f, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/, int32_t n_rows,
+                         const gsr_rows_tensor* rows, int32_t* triangles_out /*[T',3]*/, void* stream);
 size_t gsr_dist2_scratch_bytes(int32_t P);
 int gsr_dist2(int32_t P, const float* points /*[P,3]*/, float* out /*[P]*/, void* scratch, size_t scratch_bytes,
               void* stream);
