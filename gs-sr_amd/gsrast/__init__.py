@@ -75,7 +75,9 @@ EXPORTS = ["gsr_geom_bytes", "gsr_img_bytes", "gsr_binning_bytes", "gsr_backward
            "gsr_plane_allmap", "gsr_plane_allmap_backward", "gsr_gauss_activations", "gsr_gauss_activations_backward", "gsr_sample_mask_scratch_bytes", "gsr_sample_mask", "gsr_densify_stats", "gsr_adam_step", "gsr_adam_step_multi", "gsr_adam_step_multi_dev",
            "gsr_anchor_level_scratch_bytes", "gsr_anchor_level_find", "gsr_anchor_level_emit", "gsr_anchor_level_find_weed", "gsr_octree_weed_out", "gsr_rows_compact_scratch_bytes", "gsr_rows_compact_multi",
            "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_emit",
-           "gsr_mesh_post_scratch_bytes", "gsr_mesh_cluster_triangles", "gsr_mesh_filter_count", "gsr_mesh_filter_emit"]
+           "gsr_mesh_post_scratch_bytes", "gsr_mesh_cluster_triangles", "gsr_mesh_filter_count", "gsr_mesh_filter_emit",
+           "gsr_unbounded_lattice_points", "gsr_unbounded_lattice_tsdf", "gsr_unbounded_mc_scratch_bytes", "gsr_unbounded_mc_count", "gsr_unbounded_mc_emit",
+           "gsr_unbounded_finish", "gsr_unbounded_texture"]
 PROF_LABELS = ["preprocess", "depth_order", "binning", "blend_fwd", "bwd_memset", "blend_bwd", "preprocess_bwd", "_"]
 
 _lib = None
@@ -144,6 +146,20 @@ def lib():
     L.gsr_tsdf_sparse_mesh_count.argtypes = [C.POINTER(TsdfSparse), C.c_int32, _vp, C.c_float, _vp, sz, C.POINTER(C.c_uint64), _vp]
     L.gsr_tsdf_sparse_mesh_emit.restype = C.c_int
     L.gsr_tsdf_sparse_mesh_emit.argtypes = [C.POINTER(TsdfSparse), C.c_int32, _vp, C.c_float, _vp, sz, _vp, _vp, _vp, _vp]
+    L.gsr_unbounded_lattice_points.restype = C.c_int
+    L.gsr_unbounded_lattice_points.argtypes = [C.c_int32] * 3 + [_vp] * 3 + [C.POINTER(C.c_float), C.c_float, C.c_float, _vp, _vp, _vp]
+    L.gsr_unbounded_lattice_tsdf.restype = C.c_int
+    L.gsr_unbounded_lattice_tsdf.argtypes = [C.c_int32] * 3 + [_vp] * 3 + [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, _vp, C.c_int32, C.c_int32,
+                                             _vp, _vp, _vp, _vp]
+    L.gsr_unbounded_mc_scratch_bytes.restype = sz; L.gsr_unbounded_mc_scratch_bytes.argtypes = [C.c_int32] * 3
+    L.gsr_unbounded_mc_count.restype = C.c_int
+    L.gsr_unbounded_mc_count.argtypes = [C.c_int32] * 4 + [_vp, _vp, sz, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _vp]
+    L.gsr_unbounded_mc_emit.restype = C.c_int
+    L.gsr_unbounded_mc_emit.argtypes = [C.c_int32] * 4 + [_vp] * 5 + [sz, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]
+    L.gsr_unbounded_finish.restype = C.c_int
+    L.gsr_unbounded_finish.argtypes = [C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, _vp, _vp]
+    L.gsr_unbounded_texture.restype = C.c_int
+    L.gsr_unbounded_texture.argtypes = [C.c_int64, _vp, C.c_float, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]
     L.gsr_adam_step_multi.restype = C.c_int
     L.gsr_adam_step_multi.argtypes = [C.c_int32, _vp, _vp]
     L.gsr_adam_step_multi_dev.restype = C.c_int
@@ -266,3 +282,4 @@ def make_cfg(variant, P, settings, D, M, render_geo, keep):
 
 
 from .mesh import cluster_connected_triangles, post_process_mesh  # noqa: E402,F401  (gsrast.mesh needs the helpers above)
+from .unbounded import extract_mesh_unbounded  # noqa: E402,F401

@@ -616,6 +616,59 @@ int gsr_mesh_cluster_triangles(const int32_t* triangles, int64_t n_triangles, in
 int gsr_mesh_filter_count(const gsr_mesh_filter* f, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[8]*/, void* stream);
 int gsr_mesh_filter_emit(const gsr_mesh_filter* f, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/, int32_t n_rows,
                          const gsr_rows_tensor* rows, int32_t* triangles_out /*[T',3]*/, void* stream);
+/* ---- the mesh of an unbounded scene (no ABI bump: additions only).
+ * GaussianExtractor.extract_mesh_unbounded (gssr/utils/mesh_utils.py:181-277) over marching_cubes_with_contraction (gssr/utils/mcube_utils.py:17-95).
+ * THE LATTICE.  Samples live in contracted coordinates on a dense lattice with ascending float32 axes xs[nx], ys[ny], zs[nz] (device arrays), flat
+ *   index (ix * ny + iy) * nz + iz.  The reference's sample set: per axis N = resolution / crop blocks, block b samples
+ *   torch.linspace(lo_b, hi_b, crop) in float32 on the CPU with lo_b, hi_b out of np.linspace(min, max, N + 1); adjacent blocks share their boundary
+ *   sample bit for bit (a linspace starts with `start` and ends with `end`), so the lattice has N * (crop - 1) + 1 distinct planes per axis
+ *   (gsrast.unbounded.lattice_axes).  Every entry point takes arbitrary ascending axes.
+ * UN-CONTRACTION of a sample c = (x, y, z), every float32 operation rounded on its own, left to right:
+ *     mag = sqrtf(x*x + y*y + z*z);   p = mag < 1 ? c : (1 / (2 - mag)) * (c / mag) per component;   world = p * radius + center
+ *     truncation t = 5f * voxel_size, and for mag > 1:  t *= 1 / (2 - fminf(mag, 1.9f))
+ *   voxel_size = radius * 2 / resolution is the caller's (float32).  mag >= 2 gives inf or negative scales as in the reference: such a sample fails
+ *   every comparison of the update rule and stays at 1.  center: HOST float[3].
+ * gsr_unbounded_lattice_points: points [V,3] and sdf_trunc [V] of every sample, V = nx * ny * nz: what the per-frame op gsr_tsdf_integrate takes.
+ * gsr_unbounded_lattice_tsdf: ALL F frames (full_proj [F,16] row-major device array, depth [F,H,W]) over every sample in one launch: the sample is
+ *   un-contracted once, (tsdf, weight) start at (1, 1) and run through the frames IN ORDER in registers under the per-point rule of
+ *   gsr_tsdf_integrate (depth only: the reference's sdf callable discards the colours), tsdf [nx,ny,nz] is stored once.  weight == NULL: nothing else is
+ *   read or written.  weight != NULL (a further size group of a ragged frame set): tsdf and weight are read first and both written.  tsdf / weight
+ *   16-byte aligned.  Bit for bit what gsr_unbounded_lattice_points + F calls of gsr_tsdf_integrate leave in tsdf.
+ * MARCHING CUBES over a slab f [np,ny,nz] of consecutive x-planes with their axes xs[np], ys, zs; the rules of gsr_tsdf_sparse_mesh_* with every
+ *   sample counting:
+ *     case bit i = (f_i < 0) (level 0; f == 0 and NaN are outside), corners G + (i & 1, (i >> 1) & 1, (i >> 2) & 1), the same table and winding;
+ *     the lattice edge from point G along axis a carries ONE vertex iff the signs of its ends differ; its position is G's coordinates with component
+ *     a replaced by ax[g] + t * (ax[g + 1] - ax[g]), t = f0 / (f0 - f1), float32 without contraction, CONTRACTED coordinates;
+ *     vertices in order of (gx, gy, gz, axis), z fastest; triangles in order of their cube (gx, gy, gz), then table order.
+ *   A slab OWNS its first `own` planes: the vertices on edges that start there and the cubes with their origin there.  own == np: the slab ends the
+ *   lattice (its last plane has no x edges and no cubes).  Otherwise own + 2 <= np: the cubes of plane own - 1 name vertices of plane `own`, whose
+ *   numbers depend on that plane's x edges, i.e. on plane own + 1.  The next slab starts at plane `own`.  Concatenated slabs give the mesh of the whole
+ *   lattice whatever the slab size: shared planes carry identical samples, hence identical vertices, welded by edge identity -- vertices that are merely
+ *   close are never fused.  At most (2^31 - 1) / 5 numbered points ((own + 1) * ny * nz) per slab.
+ *   gsr_unbounded_mc_count: count and scan; counts_host {vertices, triangles} of the slab -- the one host synchronisation; refuses
+ *     vertex_base + vertices or triangle_base + triangles above 2^31 - 1.  scratch >= gsr_unbounded_mc_scratch_bytes(np, ny, nz), 16-byte aligned,
+ *     unmodified until the emit (4 B per numbered point + 8 B per 256 of them).
+ *   gsr_unbounded_mc_emit: vertices [n_vertices,3] (the slab's own array), triangles [n_triangles,3] holding vertex_base + the slab-local number.
+ * gsr_unbounded_finish: vertices [V,3] contracted -> world IN PLACE by the un-contraction above (no truncation), then clipped to +-max_range
+ *   componentwise in WORLD coordinates as the reference does.
+ * gsr_unbounded_texture: the reference's second fusion pass (inv_contraction=None, scalar truncation 5f * voxel_size, return_rgb=True) fused over the
+ *   frames: per vertex (tsdf, weight, rgb) = (1, 1, 0) run through the F frames in registers under the rule of gsr_tsdf_integrate (depth [F,H,W], rgb
+ *   [F,3,H,W]), colors [V,3] stored once.  Any V.  Bit for bit what F calls of gsr_tsdf_integrate leave in rgb_acc.
+ * Marching-cubes parity with skimage's Lewiner triangulation and trimesh's rounding weld is UNPINNED: the mesh is defined by the table and the rules above. */
+int gsr_unbounded_lattice_points(int32_t nx, int32_t ny, int32_t nz, const float* xs, const float* ys, const float* zs, const float* center /*host [3]*/,
+                                 float radius, float voxel_size, float* points /*[V,3]*/, float* sdf_trunc /*[V]*/, void* stream);
+int gsr_unbounded_lattice_tsdf(int32_t nx, int32_t ny, int32_t nz, const float* xs, const float* ys, const float* zs, const float* center /*host [3]*/,
+                               float radius, float voxel_size, int32_t F, const float* full_proj /*[F,16]*/, int32_t W, int32_t H,
+                               const float* depth /*[F,H,W]*/, float* tsdf /*[nx,ny,nz]*/, float* weight /*[nx,ny,nz] in/out or NULL*/, void* stream);
+size_t gsr_unbounded_mc_scratch_bytes(int32_t np, int32_t ny, int32_t nz);
+int gsr_unbounded_mc_count(int32_t np, int32_t ny, int32_t nz, int32_t own, const float* tsdf /*[np,ny,nz]*/, void* scratch, size_t scratch_bytes,
+                           int64_t vertex_base, int64_t triangle_base, uint64_t* counts_host /*[2]*/, void* stream);
+int gsr_unbounded_mc_emit(int32_t np, int32_t ny, int32_t nz, int32_t own, const float* tsdf, const float* xs /*[np]*/, const float* ys, const float* zs,
+                          const void* scratch, size_t scratch_bytes, int64_t vertex_base, int64_t n_vertices, int64_t n_triangles,
+                          float* vertices /*[n_vertices,3]*/, int32_t* triangles /*[n_triangles,3]*/, void* stream);
+int gsr_unbounded_finish(int64_t V, const float* center /*host [3]*/, float radius, float max_range, float* vertices /*[V,3] in place*/, void* stream);
+int gsr_unbounded_texture(int64_t V, const float* vertices /*[V,3] world*/, float voxel_size, int32_t F, const float* full_proj /*[F,16]*/, int32_t W,
+                          int32_t H, const float* depth /*[F,H,W]*/, const float* rgb /*[F,3,H,W]*/, float* colors /*[V,3]*/, void* stream);
 size_t gsr_dist2_scratch_bytes(int32_t P);
 int gsr_dist2(int32_t P, const float* points /*[P,3]*/, float* out /*[P]*/, void* scratch, size_t scratch_bytes,
               void* stream);
