@@ -390,6 +390,7 @@ def test_render_geo_false_plane():
 
 
 def test_visible_filter_mark_visible_dist2_tsdf():
+    # distCUDA2 and the per-point TSDF update at their size, alignment and degenerate-cloud edges: test_gpu_knn_edges.py, test_gpu_tsdf_point_edges.py
     import scaffold_filter
     from simple_knn._C import distCUDA2
     from gsrast.tsdf import tsdf_integrate_
