@@ -77,7 +77,9 @@ EXPORTS = ["gsr_geom_bytes", "gsr_img_bytes", "gsr_binning_bytes", "gsr_backward
            "gsr_densify_plan_scratch_bytes", "gsr_densify_plan", "gsr_densify_emit",
            "gsr_mesh_post_scratch_bytes", "gsr_mesh_cluster_triangles", "gsr_mesh_filter_count", "gsr_mesh_filter_emit",
            "gsr_unbounded_lattice_points", "gsr_unbounded_lattice_tsdf", "gsr_unbounded_mc_scratch_bytes", "gsr_unbounded_mc_count", "gsr_unbounded_mc_emit",
-           "gsr_unbounded_finish", "gsr_unbounded_texture"]
+           "gsr_unbounded_finish", "gsr_unbounded_texture",
+           "gsr_cam_dist_quantiles_scratch_bytes", "gsr_cam_dist_quantiles", "gsr_select_lerp_scratch_bytes", "gsr_select_lerp",
+           "gsr_voxel_unique_scratch_bytes", "gsr_voxel_unique_count", "gsr_voxel_unique_emit"]
 PROF_LABELS = ["preprocess", "depth_order", "binning", "blend_fwd", "bwd_memset", "blend_bwd", "preprocess_bwd", "_"]
 
 _lib = None
@@ -160,6 +162,17 @@ def lib():
     L.gsr_unbounded_finish.argtypes = [C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, _vp, _vp]
     L.gsr_unbounded_texture.restype = C.c_int
     L.gsr_unbounded_texture.argtypes = [C.c_int64, _vp, C.c_float, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]
+    L.gsr_cam_dist_quantiles_scratch_bytes.restype = sz; L.gsr_cam_dist_quantiles_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.gsr_cam_dist_quantiles.restype = C.c_int
+    L.gsr_cam_dist_quantiles.argtypes = [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float), _vp, _vp, sz, _vp, _vp]
+    L.gsr_select_lerp_scratch_bytes.restype = sz; L.gsr_select_lerp_scratch_bytes.argtypes = [C.c_int64]
+    L.gsr_select_lerp.restype = C.c_int
+    L.gsr_select_lerp.argtypes = [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float), _vp, _vp, sz, _vp, _vp]
+    L.gsr_voxel_unique_scratch_bytes.restype = sz; L.gsr_voxel_unique_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.gsr_voxel_unique_count.restype = C.c_int
+    L.gsr_voxel_unique_count.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, _vp, sz, _vp, _vp]
+    L.gsr_voxel_unique_emit.restype = C.c_int
+    L.gsr_voxel_unique_emit.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, _vp, sz, C.POINTER(C.c_uint32), _vp, _vp, _vp]
     L.gsr_adam_step_multi.restype = C.c_int
     L.gsr_adam_step_multi.argtypes = [C.c_int32, _vp, _vp]
     L.gsr_adam_step_multi_dev.restype = C.c_int

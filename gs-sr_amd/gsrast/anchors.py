@@ -416,3 +416,106 @@ def octree_adjust_anchor_(model, iteration, check_interval=100, success_threshol
     model._level = next(outs)
     model._extra_level = next(outs)
     return model._anchor.shape[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the first anchors
+def _initial_parameters_(model, positions, device):
+    """The O(U) fills both create_from_data end with (the reference's own torch lines): offsets, features, scaling from distCUDA2, unit quaternions, the
+    constant opacity, as fresh Parameters on the model."""
+    from simple_knn._C import distCUDA2
+    from torch import nn
+    U = positions.shape[0]
+    offsets = torch.zeros((U, model.n_offsets, 3), dtype=torch.float32, device=device)
+    anchors_feat = torch.zeros((U, model.feat_dim), dtype=torch.float32, device=device)
+    dist2 = torch.clamp_min(distCUDA2(positions).float(), 0.0000001)
+    scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 6)
+    rots = torch.zeros((U, 4), device=device)
+    rots[:, 0] = 1
+    opacities = model.inverse_opacity_activation(0.1 * torch.ones((U, 1), dtype=torch.float, device=device))
+    model._anchor = nn.Parameter(positions.requires_grad_(True))
+    model._offset = nn.Parameter(offsets.requires_grad_(True))
+    model._anchor_feat = nn.Parameter(anchors_feat.requires_grad_(True))
+    model._scaling = nn.Parameter(scales.requires_grad_(True))
+    model._rotation = nn.Parameter(rots.requires_grad_(False))
+    model._opacity = nn.Parameter(opacities.requires_grad_(False))
+
+
+def _sampling_ratio(model):
+    cfg = getattr(model, "config", None)
+    return int(getattr(cfg, "sampling_ratio", getattr(model, "sampling_ratio", 1)))
+
+
+def octree_create_from_data_(model, pcd, cameras, spatial_lr_scale):
+    """OctreeGaussian.create_from_data (octree_gaussian.py:216-253) on the device, for any object carrying the reference's attributes: dist_ratio, levels,
+    init_level, fork, extend, base_layer, visible_threshold, dist2level, n_offsets, feat_dim, inverse_opacity_activation, config.sampling_ratio (and
+    device, else "cuda").  pcd.points [N,3]; cameras {resolution scale: [camera with .camera_center]} (gsrast.init.camera_infos).  Steps: set_level
+    (per-camera distance quantiles by radix select, no C x N array); the box, base_layer, voxel_size (left a 0-dim float32 device tensor, as the
+    reference leaves it) and init_pos; octree_sample (sorted distinct cells per level); the two weed-out passes -- where visible_threshold is negative
+    the first one runs at 0 and fixes it to the mean visible fraction, the integer sum of the counts divided by U * C in float64 and cast to float32
+    (the reference's float32 torch.mean differs from it by that mean's rounding only); distCUDA2 and the parameter fills.  Leaves cam_infos,
+    standard_dist, levels, init_level, base_layer, voxel_size, init_pos, positions, visible_threshold (a float), the six Parameters, _level [U,1]
+    int32, _extra_level and _anchor_mask on the model.  Returns the number of anchors."""
+    from . import init as ginit
+    from .octree import weed_out
+    with torch.no_grad():
+        device = getattr(model, "device", "cuda")
+        points = torch.as_tensor(pcd.points[::_sampling_ratio(model)]).float().to(device)
+        fork = model.fork
+        box = (torch.min(points) * model.extend, torch.max(points) * model.extend)
+        cams, mm, host = ginit._set_level(points, cameras, model.dist_ratio, fork, extra=box)      # one host read: levels, the distances, the box
+        model.cam_infos, model.standard_dist = cams, mm[1]
+        if model.levels == -1:
+            if not math.isfinite(host[0]):
+                raise RuntimeError("octree_create_from_data_: dist_max / dist_min is not a positive finite number, levels cannot be derived")
+            model.levels = int(host[0]) + 1
+        if model.init_level == -1:
+            model.init_level = int(model.levels / 2)
+        model.spatial_lr_scale = spatial_lr_scale
+        box_min, box_max = torch.tensor(host[3], dtype=torch.float32), torch.tensor(host[4], dtype=torch.float32)      # the device's float32 values, exactly
+        box_d = box_max - box_min
+        if model.base_layer < 0:
+            default_voxel_size = 0.02
+            model.base_layer = torch.round(torch.log2(box_d / default_voxel_size)).int().item() - (model.levels // 2) + 1
+        voxel_size = box_d / (float(fork) ** model.base_layer)
+        init_pos = torch.stack([box_min, box_min, box_min]).float()
+        model.voxel_size, model.init_pos = voxel_size.to(device), init_pos.to(device)
+        positions, level = ginit.octree_sample(points, init_pos, voxel_size, fork, model.levels)
+        standard_dist = C.c_float(host[2]).value
+        Cn = cams.shape[0]
+        if model.visible_threshold < 0:
+            count, keep = weed_out(positions, level, cams, standard_dist, fork, model.levels, model.dist2level, 0.0)
+            total = int(count.sum(dtype=torch.int64).item())
+            model.visible_threshold = C.c_float(total / (float(positions.shape[0]) * Cn)).value
+            positions, level = positions[keep], level[keep]
+        _, keep = weed_out(positions, level, cams, standard_dist, fork, model.levels, model.dist2level, float(model.visible_threshold))
+        positions, level = positions[keep].contiguous(), level[keep].contiguous()
+        model.positions = positions
+        _initial_parameters_(model, positions, device)
+        model._level = level.unsqueeze(dim=1)
+        model._extra_level = torch.zeros(positions.shape[0], dtype=torch.float, device=device)
+        model._anchor_mask = torch.ones(positions.shape[0], dtype=torch.bool, device=device)
+        return positions.shape[0]
+
+
+def create_from_data_(model, pcd, cameras, spatial_lr_scale):
+    """ScaffoldGaussian.create_from_data (scaffold_gaussian.py:262-298) on the device, for any object carrying voxel_size, n_offsets, feat_dim,
+    inverse_opacity_activation, config.sampling_ratio (and device, else "cuda").  Where voxel_size <= 0 it becomes the median of distCUDA2 over the
+    cloud, torch.kthvalue(dist, int(N * 0.5)), by radix select (gsrast.init.kthvalue).  The distinct voxels come from gsrast.init.voxelize_sample: on
+    the device, in the precision of pcd.points as numpy would compute them, without the round trip through the host.  The reference shuffles
+    pcd.points IN PLACE (np.random.shuffle) before np.unique; this function does not touch the caller's array, and its rows are the same set in
+    the same (sorted) order.  `cameras` is not read, as in the reference.  Returns the number of anchors."""
+    from simple_knn._C import distCUDA2
+    from . import init as ginit
+    with torch.no_grad():
+        device = getattr(model, "device", "cuda")
+        model.spatial_lr_scale = spatial_lr_scale
+        points = pcd.points[::_sampling_ratio(model)]
+        if model.voxel_size <= 0:
+            init_points = torch.as_tensor(points).float().to(device)
+            init_dist = distCUDA2(init_points).float()
+            model.voxel_size = ginit.kthvalue(init_dist, int(init_dist.shape[0] * 0.5)).item()
+            del init_dist, init_points
+        positions = ginit.voxelize_sample(points, model.voxel_size, device)
+        _initial_parameters_(model, positions, device)
+        model.max_radii2D = torch.zeros((positions.shape[0]), device=device)
+        return positions.shape[0]

@@ -673,6 +673,44 @@ size_t gsr_dist2_scratch_bytes(int32_t P);
 int gsr_dist2(int32_t P, const float* points /*[P,3]*/, float* out /*[P]*/, void* scratch, size_t scratch_bytes,
               void* stream);
 
+/* ---- anchors from the point cloud (OctreeGaussian.create_from_data: set_level, octree_sample, octree_gaussian.py:152-182; ScaffoldGaussian.
+ * create_from_data: voxelize_sample, scaffold_gaussian.py:257-298; additions, no ABI bump).  N, n < 2^31.  status words are cleared by the call
+ * and carry GSR_INIT_ERR_* bits afterwards; the host wrapper reads them with its results and raises.
+ * gsr_cam_dist_quantiles: per camera c (cam_infos row: centre, scale), over dist_i = sqrt(((dx*dx + dy*dy) + dz*dz)) in float32 with every
+ *   operation rounded on its own, the two interpolated order statistics torch.quantile gives:
+ *     all_dist[2c + t] = lerp(sorted[k_lo[t]], sorted[k_hi[t]], w[t]) * scale,   t = 0 ("min", q = 1 - dist_ratio), 1 ("max", q = dist_ratio)
+ *   k_lo, k_hi (0-based, k_lo <= k_hi <= k_lo + 1 < N) and w are HOST arrays of two; the caller derives them as ATen does (rank = float32(q) *
+ *   (N - 1) in float32, floor, ceil, weight = rank - floor).  lerp is ATen's Lerp.h: w < 0.5 ? a + w * (b - a) : b - (b - a) * (1 - w), every
+ *   operation rounded on its own.  The C x N distances are never stored: radix select over the bits of the squared distance, recomputed in each of four passes;
+ *   scratch is O(C).  A point or camera that makes a distance non-finite sets GSR_INIT_ERR_NONFINITE.
+ * gsr_select_lerp: the same select and lerp over a float array (any sign; NaN sets GSR_INIT_ERR_NONFINITE): out[t] for n_targets = 1 or 2 targets.
+ *   n_dev (or NULL): the device-side element count, n is then the most it can be; a rank at or beyond it sets GSR_INIT_ERR_RANK.
+ * gsr_voxel_unique_*: for each of L <= 32 cell sizes the distinct rows of key = rint((p - init_pos) / cell_l) per axis (subtract, IEEE divide,
+ *   half to even, in the precision of the points: mode GSR_VOXEL_F32 float points, GSR_VOXEL_F64 double points; init_pos and cell are HOST
+ *   doubles converted to that precision).  Keys are any int32; a quotient beyond sets GSR_INIT_ERR_KEY_RANGE, a non-finite coordinate
+ *   GSR_INIT_ERR_NONFINITE.  count: record_dev [1 + L] = {status, rows of level 0, 1, ...}; the run heads stay in scratch.  emit (record: the
+ *   HOST copy of those words, status 0): positions [sum, 3] = (float)(key * cell_l + init_pos) (multiply, then add; a zero key gives +0) and
+ *   level [sum] = l, levels in ascending order, within a level rows ascending by x, then y, then z (torch.unique(dim=0) / np.unique(axis=0)). */
+#define GSR_INIT_ERR_NONFINITE 1u
+#define GSR_INIT_ERR_KEY_RANGE 2u
+#define GSR_INIT_ERR_RANK 4u
+#define GSR_VOXEL_F32 0
+#define GSR_VOXEL_F64 1
+size_t gsr_cam_dist_quantiles_scratch_bytes(int64_t N, int32_t C);
+int gsr_cam_dist_quantiles(const float* points /*[N,3]*/, int64_t N, const float* cam_infos /*[C,4]*/, int32_t C, const int64_t* k_lo /*host [2]*/,
+                           const int64_t* k_hi /*host [2]*/, const float* w /*host [2]*/, float* all_dist /*[2C]*/, void* scratch, size_t scratch_bytes,
+                           uint32_t* status_dev /*[1]*/, void* stream);
+size_t gsr_select_lerp_scratch_bytes(int64_t n);
+int gsr_select_lerp(const float* values /*[n]*/, int64_t n, const uint32_t* n_dev /*or NULL*/, int32_t n_targets, const int64_t* k_lo /*host*/,
+                    const int64_t* k_hi /*host*/, const float* w /*host*/, float* out /*[n_targets]*/, void* scratch, size_t scratch_bytes,
+                    uint32_t* status_dev /*[1]*/, void* stream);
+size_t gsr_voxel_unique_scratch_bytes(int64_t N, int32_t L);
+int gsr_voxel_unique_count(const void* points /*[N,3]*/, int64_t N, int32_t L, const double* init_pos /*host [3]*/, const double* cell /*host [L]*/,
+                           int32_t mode, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[1 + L]*/, void* stream);
+int gsr_voxel_unique_emit(const void* points, int64_t N, int32_t L, const double* init_pos, const double* cell, int32_t mode, const void* scratch,
+                          size_t scratch_bytes, const uint32_t* record /*host [1 + L]*/, float* positions /*[sum,3]*/, int32_t* level /*[sum]*/,
+                          void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
