@@ -1,4 +1,4 @@
-// gsr_anchor.hip -- Scaffold-GS / Octree-GS densification geometry on the device (include/gsrast.h gsr_anchor_*, gsr_rows_*).
+// gsr_anchor.hip -- Scaffold-GS / Octree-GS densification geometry on the device (include/gsrast.h gsr_anchor_*).
 //
 // One growing level (ScaffoldGaussian.anchor_growing, gssr/gaussian/scaffold_gaussian.py:555-649; the loop body of OctreeGaussian.anchor_growing,
 // octree_gaussian.py:401-534): the reference compares every unique candidate cell against every anchor (O(U N), chunks of 4096), after a
@@ -9,11 +9,9 @@
 //
 // This unit is built with -ffp-contract=off: the cell of a point is an integer output and must not depend on FMA contraction.
 #include "gsr_common.h"
-#include "gsr_scan.h"
+#include "gsr_compact.h"
 #include <cmath>
-#include <vector>
 
-#define ANC_BLOCK 1024
 #define ANC_BIAS 1048576            // 2^20: cells in [-2^20, 2^20 - 1] per axis
 #define ANC_CNT_ENTRIES 0           // counters: entries in the sort
 #define ANC_CNT_HEADS 1             //           new anchors
@@ -60,30 +58,14 @@ __device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L,
     return true;
 }
 
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_count(gsr_anchor_level L, const uint8_t* __restrict__ occupy, uint32_t cap, uint32_t* __restrict__ sums,
-                                                               uint32_t* __restrict__ status)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
+// the compaction (gsr_compact.h) of the entries that take part: anc_entry runs in both passes (its sticky atomicOr is idempotent)
+struct AncEntryOp {
+    gsr_anchor_level L; const uint8_t* occupy; uint32_t *status, *key_lo, *key_hi, *sort_keys, *src;
     uint64_t key;
-    const uint32_t f = (i < cap && anc_entry(i, L, occupy, &key, status)) ? 1u : 0u;
-    uint32_t tot;
-    block_excl_scan(f, lds, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_entry_place(gsr_anchor_level L, const uint8_t* __restrict__ occupy, uint32_t cap,
-                                                               const uint32_t* __restrict__ sums, uint32_t* __restrict__ status, uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi, uint32_t* __restrict__ sort_keys,
-                                                               uint32_t* __restrict__ src)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    uint64_t key = 0;
-    const bool f = i < cap && anc_entry(i, L, occupy, &key, status);
-    uint32_t tot;
-    const uint32_t pos = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);       // < cap: at most one position per entry
-    if (f) { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
-}
+    __device__ bool keep(uint32_t i) { return anc_entry(i, L, occupy, &key, status); }
+    // pos < capacity: at most one position per entry
+    __device__ void place(uint32_t i, uint32_t pos) const { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
+};
 
 __global__ void __launch_bounds__(256) k_anc_gather_hi(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_hi,
                                                        uint32_t* __restrict__ keys)
@@ -103,26 +85,11 @@ __device__ __forceinline__ bool anc_is_head(uint32_t p, uint32_t n, const uint32
     return (q >> 1) != (k >> 1);
 }
 
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_count(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm,
-                                                              const uint32_t* __restrict__ key_lo, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t f = anc_is_head(blockIdx.x * ANC_BLOCK + threadIdx.x, *n_dev, hi, perm, key_lo) ? 1u : 0u;
-    uint32_t tot;
-    block_excl_scan(f, lds, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_head_place(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm,
-                                                              const uint32_t* __restrict__ key_lo, const uint32_t* __restrict__ sums, uint32_t* __restrict__ head_pos)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t p = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    const bool f = anc_is_head(p, *n_dev, hi, perm, key_lo);
-    uint32_t tot;
-    const uint32_t q = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);        // q <= p < capacity
-    if (f) head_pos[q] = p;
-}
+struct AncHeadOp {
+    const uint32_t *n_dev, *hi, *perm, *key_lo; uint32_t* head_pos;
+    __device__ bool keep(uint32_t p) const { return anc_is_head(p, *n_dev, hi, perm, key_lo); }
+    __device__ void place(uint32_t p, uint32_t q) const { head_pos[q] = p; }      // q <= p < capacity
+};
 
 __global__ void __launch_bounds__(64) k_anc_publish(const uint32_t* __restrict__ counters, uint32_t* __restrict__ status)
 {
@@ -203,25 +170,12 @@ __global__ void __launch_bounds__(WEED_BLOCK) k_anc_weed_flag(gsr_anchor_level L
     if (active) { heads[q] = p; flag[q] = weed_keep(v, W) ? 1u : 0u; }
 }
 
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_weed_count(const uint32_t* __restrict__ counters, const uint32_t* __restrict__ flag, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t q = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    uint32_t tot;
-    block_excl_scan((q < counters[ANC_CNT_HEADS] && flag[q]) ? 1u : 0u, lds, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(ANC_BLOCK) k_anc_weed_place(const uint32_t* __restrict__ counters, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ heads,
-                                                              const uint32_t* __restrict__ sums, uint32_t* __restrict__ head_pos)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t q = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    const bool f = q < counters[ANC_CNT_HEADS] && flag[q];
-    uint32_t tot;
-    const uint32_t w = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);        // w <= q < capacity
-    if (f) head_pos[w] = heads[q];
-}
+// the heads whose flag is set, back into head_pos
+struct AncWeedOp {
+    const uint32_t *counters, *flag, *heads; uint32_t* head_pos;
+    __device__ bool keep(uint32_t q) const { return q < counters[ANC_CNT_HEADS] && flag[q]; }
+    __device__ void place(uint32_t q, uint32_t w) const { head_pos[w] = heads[q]; }      // w <= q < capacity
+};
 
 // the weeded count takes the place of the head count (gsr_anchor_level_emit reads it); status = {final, overflow (sticky), found before the weed-out}
 __global__ void __launch_bounds__(64) k_anc_publish_weed(uint32_t* __restrict__ counters, uint32_t* __restrict__ status, int weeded)
@@ -266,17 +220,16 @@ __global__ void __launch_bounds__(256) k_anc_emit(gsr_anchor_level L, uint32_t c
 }
 
 struct AncScratch { uint32_t *sums, *key_lo, *key_hi, *src, *ka, *kb, *va, *vb, *hist, *counters; size_t bytes; };
-static AncScratch anc_carve(uint32_t cap, void* base)
+static AncScratch anc_carve(uint32_t cap, const void* base)
 {
-    AncScratch a; char* p = (char*)base;
+    AncScratch a; GsrCarve c(base);
     const size_t n = cap > 0 ? cap : 1;
-    auto take = [&](size_t bytes) { char* r = p; p += gsr_align(bytes); return (uint32_t*)r; };
-    a.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4);
-    a.key_lo = take(n * 4); a.key_hi = take(n * 4); a.src = take(n * 4);
-    a.ka = take(n * 4); a.kb = take(n * 4); a.va = take(n * 4); a.vb = take(n * 4);
-    a.hist = take(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256) * 4);
-    a.counters = take(64);
-    a.bytes = (size_t)(p - (char*)base);
+    a.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
+    a.key_lo = c.take<uint32_t>(n); a.key_hi = c.take<uint32_t>(n); a.src = c.take<uint32_t>(n);
+    a.ka = c.take<uint32_t>(n); a.kb = c.take<uint32_t>(n); a.va = c.take<uint32_t>(n); a.vb = c.take<uint32_t>(n);
+    a.hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256));
+    a.counters = c.take<uint32_t>(16);
+    a.bytes = c.bytes();
     return a;
 }
 
@@ -328,14 +281,11 @@ static int anc_find(const char* who, const gsr_anchor_level* lv, const uint8_t* 
     if (weed && weed_check(weed, who, &W)) return 1;
     if (!status_dev) { gsr_set_error("%s: status_dev is NULL", who); return 1; }
     const AncScratch a = anc_carve(cap, scratch);
-    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, a.bytes); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, a.bytes, false)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(a.counters, 0, 64, s)) { gsr_set_error("%s: counters", who); return 1; }
     if (cap) {
-        const uint32_t nblk = gsr_div_up(cap, ANC_BLOCK);
-        hipLaunchKernelGGL(k_anc_entry_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, occupy, cap, a.sums, status_dev);
-        gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_ENTRIES, nullptr, s);
-        hipLaunchKernelGGL(k_anc_entry_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, *lv, occupy, cap, a.sums, status_dev, a.key_lo, a.key_hi, a.ka, a.src);
+        gsr_compact(AncEntryOp{*lv, occupy, status_dev, a.key_lo, a.key_hi, a.ka, a.src, 0}, cap, a.sums, a.counters + ANC_CNT_ENTRIES, s);
         const uint32_t* n_dev = a.counters + ANC_CNT_ENTRIES;
         uint32_t *k0 = a.ka, *v0 = a.va, *k1 = a.kb, *v1 = a.vb;
         bool in_b = false;
@@ -346,18 +296,14 @@ static int anc_find(const char* who, const gsr_anchor_level* lv, const uint8_t* 
         if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
         // both sorts run 4 passes of 8 bits: the order ends in (ka, va), the run heads go to kb -- gsr_anchor_level_emit relies on it
         if (k0 != a.ka || v0 != a.va) { gsr_set_error("%s: unexpected sort buffer parity", who); return 1; }
-        hipLaunchKernelGGL(k_anc_head_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums);
-        gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_HEADS, nullptr, s);
-        hipLaunchKernelGGL(k_anc_head_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, n_dev, a.ka, a.va, a.key_lo, a.sums, a.kb);
+        gsr_compact(AncHeadOp{n_dev, a.ka, a.va, a.key_lo, a.kb}, cap, a.sums, a.counters + ANC_CNT_HEADS, s);
         if (weed) {
             // heads <= candidate slots; key_hi (consumed by the gather) keeps the unweeded heads, vb (free: the order ended in ka / va) the flags
             const uint32_t worst = (uint32_t)lv->N0 * (uint32_t)lv->k;
             if (worst) {
                 hipLaunchKernelGGL(k_anc_weed_flag, dim3(gsr_div_up(worst, WEED_BLOCK)), dim3(WEED_BLOCK), 0, s, *lv, W, weed->lv, a.counters, a.ka, a.va, a.key_lo,
                                    a.kb, a.key_hi, a.vb);
-                hipLaunchKernelGGL(k_anc_weed_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, a.counters, a.vb, a.sums);
-                gsr_scan_small(a.sums, nblk, 1, 0, a.counters + ANC_CNT_FOUND, nullptr, s);
-                hipLaunchKernelGGL(k_anc_weed_place, dim3(nblk), dim3(ANC_BLOCK), 0, s, a.counters, a.vb, a.key_hi, a.sums, a.kb);
+                gsr_compact(AncWeedOp{a.counters, a.vb, a.key_hi, a.kb}, cap, a.sums, a.counters + ANC_CNT_FOUND, s);
             }
         }
     }
@@ -396,8 +342,8 @@ extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scr
 {
     uint32_t cap;
     if (anc_check(lv, "anchor_level_emit", &cap)) return 1;
-    const AncScratch a = anc_carve(cap, const_cast<void*>(scratch));
-    if (!scratch || a.bytes > scratch_bytes) { gsr_set_error("anchor_level_emit: scratch too small: %zu < %zu", scratch_bytes, a.bytes); return 1; }
+    const AncScratch a = anc_carve(cap, scratch);
+    if (gsr_scratch_check("anchor_level_emit", scratch, scratch_bytes, a.bytes, false)) return 1;
     if (count == 0) return 0;
     if (count > (uint32_t)lv->N0 * (uint32_t)lv->k) { gsr_set_error("anchor_level_emit: count %u exceeds the N0 * k candidate slots", count); return 1; }
     if (!new_anchor || (lv->F && !new_feat)) { gsr_set_error("anchor_level_emit: new_anchor / new_feat is NULL"); return 1; }
@@ -406,70 +352,4 @@ extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scr
     hipLaunchKernelGGL(k_anc_emit, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lv, count, a.counters, a.ka, a.va, a.key_lo, a.src,
                        a.kb, new_anchor, new_feat);
     return gsr_check_launch("anchor_level_emit", (hipStream_t)stream, false);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- rows: compact + append
-// dst = [src[keep] ; tail] for many tensors that share one keep mask over N rows (the reference's per-tensor x[mask] + cat over six parameters,
-// twelve Adam moments and four accumulators: ~60 launches and a nonzero() synchronisation each).  The keep -> position scan runs once and leaves
-// map[position] = row for every kept row; the row mover (gsr_rows.hip) does the rest, with the number kept read on the device.
-__global__ void __launch_bounds__(ANC_BLOCK) k_rows_count(const uint8_t* __restrict__ keep, uint32_t N, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    uint32_t tot;
-    block_excl_scan((i < N && keep[i]) ? 1u : 0u, lds, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(ANC_BLOCK) k_rows_map(const uint8_t* __restrict__ keep, uint32_t N, const uint32_t* __restrict__ sums, uint32_t* __restrict__ map,
-                                                        uint32_t* __restrict__ rank)
-{
-    __shared__ uint32_t lds[17];
-    const uint32_t i = blockIdx.x * ANC_BLOCK + threadIdx.x;
-    const bool f = i < N && keep[i];
-    uint32_t tot;
-    const uint32_t p = sums[blockIdx.x] + block_excl_scan(f ? 1u : 0u, lds, &tot);          // p <= i < N
-    if (f && map) map[p] = i;
-    if (f && rank) rank[i] = p;
-}
-// The keep scan on its own (gsr_common.h): block counts, k_scan_small, placement.  sums holds ceil(N / 1024) + 1 words.
-void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_t* map, uint32_t* rank, uint32_t* count_dev, hipStream_t s)
-{
-    const uint32_t nblk = gsr_div_up(N > 0 ? N : 1u, ANC_BLOCK);
-    hipLaunchKernelGGL(k_rows_count, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, N, sums);
-    gsr_scan_small(sums, nblk, 1, 0, count_dev, nullptr, s);
-    hipLaunchKernelGGL(k_rows_map, dim3(nblk), dim3(ANC_BLOCK), 0, s, keep, N, sums, map, rank);
-}
-
-struct RowsScratch { uint32_t *sums, *map, *count; size_t bytes; };
-static RowsScratch rows_carve(uint32_t N, void* base)
-{
-    RowsScratch r; char* p = (char*)base;
-    const size_t n = N > 0 ? N : 1;
-    auto take = [&](size_t bytes) { char* q = p; p += gsr_align(bytes); return (uint32_t*)q; };
-    r.sums = take(((size_t)gsr_div_up((uint32_t)n, ANC_BLOCK) + 1) * 4); r.map = take(n * 4); r.count = take(64);
-    r.bytes = (size_t)(p - (char*)base);
-    return r;
-}
-extern "C" size_t gsr_rows_compact_scratch_bytes(int64_t N)
-{
-    if (N < 0 || N >= (1ll << 31)) return 0;
-    return rows_carve((uint32_t)N, nullptr).bytes;
-}
-
-extern "C" int gsr_rows_compact_multi(int64_t N, const uint8_t* keep, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
-                                      void* stream)
-{
-    const char* who = "rows_compact_multi";
-    if (N < 0 || N >= (1ll << 31)) { gsr_set_error("%s: N=%lld out of range", who, (long long)N); return 1; }
-    if (N > 0 && !keep) { gsr_set_error("%s: keep is NULL", who); return 1; }
-    const RowsScratch r = rows_carve((uint32_t)N, scratch);
-    if (!scratch || r.bytes > scratch_bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, r.bytes); return 1; }
-    std::vector<gsr_rows_item> items;
-    for (int32_t i = 0; t && i < count; i++) items.push_back({t[i].src, t[i].dst, t[i].tail, t[i].row_bytes, t[i].n_tail, false});
-    const gsr_rows_map m = {r.map, r.count, (uint32_t)N, 0u, (uint32_t)N};
-    hipStream_t s = (hipStream_t)stream;
-    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, false, s)) return 1;                      // the checks, before anything is launched
-    gsr_rows_keep_scan(keep, (uint32_t)N, r.sums, r.map, nullptr, r.count, s);
-    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, true, s)) return 1;
-    return gsr_check_launch(who, s, false);
 }

@@ -48,17 +48,10 @@ void gsr_scan_small(uint32_t* data, uint32_t n, uint32_t rows, uint32_t stride, 
 __global__ void __launch_bounds__(256) k_scan_rows(uint32_t* __restrict__ data, uint32_t cols, uint32_t* __restrict__ tot)
 {
     __shared__ uint32_t lds[17];
-    uint32_t* row = data + (size_t)blockIdx.x * cols;
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < cols; c0 += 256) {
-        const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = (i < cols) ? row[i] : 0;
-        uint32_t t;
-        const uint32_t incl = block_incl_scan(v, lds, &t);
-        if (i < cols) row[i] = carry + incl - v;
-        carry += t;
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+    uint32_t* const row[1] = { data + (size_t)blockIdx.x * cols };
+    unsigned long long total[1] = { 0ull };
+    block_scan_arrays<256, 1>(row, cols, lds, total);
+    if (threadIdx.x == 0) tot[blockIdx.x] = (uint32_t)total[0];
 }
 
 // ------------------------------------------------------------------------------------------------ radix sort

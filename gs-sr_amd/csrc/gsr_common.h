@@ -47,6 +47,15 @@ static inline __host__ __device__ int gsr_acc_stride(int variant)
 static inline __host__ __device__ size_t gsr_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline __host__ __device__ uint32_t gsr_div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
+// Scratch carving: consecutive arrays, each starting on a 256-byte boundary of the caller's block.  With a NULL base only bytes() means
+// anything (the *_scratch_bytes functions).
+struct GsrCarve {
+    char* base; size_t cur;
+    explicit GsrCarve(const void* b) : base((char*)const_cast<void*>(b)), cur(0) {}
+    template <typename T> T* take(size_t count) { T* r = reinterpret_cast<T*>(base + cur); cur += gsr_align(count * sizeof(T)); return r; }
+    size_t bytes() const { return cur; }
+};
+
 // ---- arena views -------------------------------------------------------------------------------------------
 struct GeomView {
     uint32_t* depth_key;      // [P]  bit pattern of view-space depth; 0xFFFFFFFF for culled gaussians
@@ -95,6 +104,13 @@ ImgView gsr_carve_img(int variant, int W, int H, void* base);
 // ---- error plumbing ----------------------------------------------------------------------------------------
 void gsr_set_error(const char* fmt, ...);
 int gsr_check_launch(const char* what, hipStream_t s, bool debug);
+// the scratch block holds `need` bytes and, where the entry point's contract says so (`aligned`), starts on a 16-byte boundary; else the error is set and 1 returned
+static inline int gsr_scratch_check(const char* who, const void* scratch, size_t given, size_t need, bool aligned = true)
+{
+    if (scratch && given >= need && !(aligned && ((uintptr_t)scratch & 15))) return 0;
+    gsr_set_error("%s: scratch too small: scratch of %zu bytes%s needed, %zu given", who, need, aligned ? " (16-byte aligned)" : "", given);
+    return 1;
+}
 #define GSR_CHECK(call, what)                                                                \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
@@ -181,6 +197,20 @@ struct gsr_rows_item { const void* src; void* dst; const void* tail; int64_t row
 struct gsr_rows_map { const uint32_t* map; const uint32_t* n_map_dev; uint32_t n_map, n_carried, src_rows; };
 // Checks the table (errors are prefixed with `who`), then launches unless !launch: an entry point with kernels of its own in front validates first.
 int gsr_rows_move(const char* who, const gsr_rows_map& m, int32_t count, const gsr_rows_item* t, bool launch, hipStream_t s);
-// The keep scan of the row compaction on its own (gsr_anchor.hip): for every i < N with keep[i], p = the number of kept rows in front of it;
-// map[p] = i and rank[i] = p (either may be NULL), *count_dev = the number kept.  Count / scan / place passes; sums: ceil(N / 1024) + 1 words.
+// The count / scan / place compaction (gsr_compact.h): workgroups of GSR_COMPACT_BLOCK elements, one word of `sums` each and one for the total.
+#define GSR_COMPACT_BLOCK 1024
+static inline size_t gsr_compact_sums_words(size_t n) { return (n > 0 ? (n + GSR_COMPACT_BLOCK - 1) / GSR_COMPACT_BLOCK : 1) + 1; }
+// The keep scan of the row compaction on its own (gsr_rows.hip): for every i < N with keep[i], p = the number of kept rows in front of it;
+// map[p] = i and rank[i] = p (either may be NULL), *count_dev = the number kept.  sums: gsr_compact_sums_words(N) words.
 void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_t* map, uint32_t* rank, uint32_t* count_dev, hipStream_t s);
+
+// The radix select (gsr_init.hip): up to four order statistics of one array, MSB first, 8 bits per pass: four times a histogram kernel and
+// a one-workgroup advance.  rank[t] is 0-based in ascending key order; the keys are the first min(n, *n_dev) values (n alone where n_dev is
+// NULL).  GSR_SELECT_FLOAT: float32 values (a NaN sets GSR_INIT_ERR_NONFINITE in *status); GSR_SELECT_U32_DESC: uint32 values in
+// DESCENDING order, so that rank k - 1 is the k-th largest.  Afterwards word t of `state` holds the KEY of rank t: the float's bit pattern
+// folded to unsigned order, or the complement of the uint32 value.  A rank beyond the keys sets GSR_INIT_ERR_RANK in *status.  The caller
+// clears the GSR_SELECT_STATE_BYTES of `state` and *status on the stream beforehand.
+#define GSR_SELECT_FLOAT 0
+#define GSR_SELECT_U32_DESC 1
+#define GSR_SELECT_STATE_BYTES (2 * 256 + 4 * 256 * 4)
+void gsr_select(int kind, const void* values, uint32_t n, const uint32_t* n_dev, const uint32_t rank[4], uint32_t* state, uint32_t* status, hipStream_t s);

@@ -153,18 +153,15 @@ __global__ void __launch_bounds__(256) k_den_compute(gsr_densify_args A, gsr_den
 
 // ---------------------------------------------------------------------------------------------------------------- host
 struct DenScratch { uint8_t* flags; uint32_t *rank, *sums, *counters, *map; uint32_t nblk, stride; size_t bytes; };
-static DenScratch den_carve(uint32_t P, uint32_t N, void* base)
+static DenScratch den_carve(uint32_t P, uint32_t N, const void* base)
 {
-    DenScratch d; char* p = (char*)base;
+    DenScratch d; GsrCarve c(base);
     const size_t n = P > 0 ? P : 1;
-    auto take = [&](size_t bytes) { char* r = p; p += gsr_align(bytes); return r; };
     d.nblk = gsr_div_up((uint32_t)n, DEN_BLOCK); d.stride = d.nblk + 1;
-    d.flags = (uint8_t*)take(n);
-    d.rank = (uint32_t*)take(n * 4);
-    d.sums = (uint32_t*)take((size_t)DEN_NQ * d.stride * 4);
-    d.counters = (uint32_t*)take(DEN_CNT * 4);
-    d.map = (uint32_t*)take(n * (N > 2 ? N : 2) * 4);
-    d.bytes = (size_t)(p - (char*)base);
+    d.flags = c.take<uint8_t>(n); d.rank = c.take<uint32_t>(n);
+    d.sums = c.take<uint32_t>((size_t)DEN_NQ * d.stride); d.counters = c.take<uint32_t>(DEN_CNT);
+    d.map = c.take<uint32_t>(n * (N > 2 ? N : 2));
+    d.bytes = c.bytes();
     return d;
 }
 
@@ -194,7 +191,7 @@ extern "C" int gsr_densify_plan(const gsr_densify_args* a, void* scratch, size_t
     if (den_check(a, "densify_plan")) return 1;
     if (!status_dev) { gsr_set_error("densify_plan: status_dev is NULL"); return 1; }
     const DenScratch d = den_carve((uint32_t)a->P, (uint32_t)a->N, scratch);
-    if (!scratch || d.bytes > scratch_bytes) { gsr_set_error("densify_plan: scratch too small: %zu < %zu", scratch_bytes, d.bytes); return 1; }
+    if (gsr_scratch_check("densify_plan", scratch, scratch_bytes, d.bytes, false)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(status_dev, 0, 8 * 4, s) || gsr_memset_async(d.counters, 0, DEN_CNT * 4, s)) { gsr_set_error("densify_plan: counters"); return 1; }
     if (a->P) {
@@ -210,8 +207,8 @@ extern "C" int gsr_densify_emit(const gsr_densify_args* a, const void* scratch, 
 {
     if (den_check(a, "densify_emit")) return 1;
     if (!counts) { gsr_set_error("densify_emit: counts is NULL"); return 1; }
-    const DenScratch d = den_carve((uint32_t)a->P, (uint32_t)a->N, const_cast<void*>(scratch));
-    if (!scratch || d.bytes > scratch_bytes) { gsr_set_error("densify_emit: scratch too small: %zu < %zu", scratch_bytes, d.bytes); return 1; }
+    const DenScratch d = den_carve((uint32_t)a->P, (uint32_t)a->N, scratch);
+    if (gsr_scratch_check("densify_emit", scratch, scratch_bytes, d.bytes, false)) return 1;
     const uint32_t P = (uint32_t)a->P, N = (uint32_t)a->N;
     const uint32_t C = counts[0], S = counts[1], nO = counts[2], nC = counts[3], nS = counts[4];
     if (C > P || S > P - C || nO > P - S || nC > C || nS > S) { gsr_set_error("densify_emit: counts are not those of a plan over P=%u rows", P); return 1; }

@@ -13,7 +13,8 @@
 //               Pass 0 meets few bins (the top 8 bits are sign + 7 exponent bits): the histograms are private to a wave there, and lanes that
 //               share the wave's leading bin add once (CQ_AGG rounds), the rest by LDS atomics.  The root is taken of the selected values only
 //               (a correctly rounded sqrt is monotone), then ATen's lerp and the camera's scale.
-//   arrays      k_sel_hist: the same select over a float array (sign-magnitude keys folded to unsigned order).
+//   arrays      k_sel_hist: the same select over an array (gsr_select, gsr_common.h): floats with their sign-magnitude patterns folded to unsigned
+//               order, or uint32 complemented for a descending order (the mesh filter's k-th largest cluster, gsr_mesh_post.hip).
 //   voxels      per cell size: key = rint((p - init_pos) / cell) per axis (IEEE divide, half to even), three stable LSD sorts (z, y, x) of the
 //               sign-biased int32 keys with gsr_radix_sort_pairs, run heads by the keep scan; the heads' point indices stay in scratch for the emit.
 // lerp: ATen's Lerp.h, w < 0.5 ? a + w * (b - a) : b - (b - a) * (1 - w), every operation rounded on its own (PRE_FLAGS: no contraction).  That is what
@@ -182,8 +183,20 @@ __global__ void __launch_bounds__(SEL_BLOCK) k_cq_finish(const float* __restrict
 __device__ __forceinline__ uint32_t sel_fold(uint32_t bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 __device__ __forceinline__ uint32_t sel_unfold(uint32_t key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
 
-__global__ void __launch_bounds__(SEL_BLOCK) k_sel_hist(const float* __restrict__ values, uint32_t n, const uint32_t* __restrict__ n_dev, SelState st, int pass,
-                                                        uint32_t* __restrict__ status)
+// the key of element i in ascending unsigned order; *bad where the element has none
+struct SelKeyFloat {
+    const float* v;
+    __device__ uint32_t operator()(uint32_t i, bool* bad) const
+    {
+        const uint32_t bits = __float_as_uint(v[i]);
+        if ((bits & 0x7FFFFFFFu) > 0x7F800000u) *bad = true;              // NaN
+        return sel_fold(bits);
+    }
+};
+struct SelKeyU32Desc { const uint32_t* v; __device__ uint32_t operator()(uint32_t i, bool*) const { return ~v[i]; } };      // descending: no value is bad
+
+template <typename Key>
+__global__ void __launch_bounds__(SEL_BLOCK) k_sel_hist(Key key_of, uint32_t n, const uint32_t* __restrict__ n_dev, SelState st, int pass, uint32_t* __restrict__ status)
 {
     __shared__ uint32_t h[SEL_RANKS * 256];
     __shared__ uint32_t pfx[SEL_RANKS];
@@ -195,9 +208,7 @@ __global__ void __launch_bounds__(SEL_BLOCK) k_sel_hist(const float* __restrict_
     const uint32_t himask = pass ? ~0u << (32 - 8 * pass) : 0u;
     bool bad = false;
     for (uint32_t i = blockIdx.x * SEL_BLOCK + threadIdx.x; i < n; i += gridDim.x * SEL_BLOCK) {
-        const uint32_t bits = __float_as_uint(values[i]);
-        if ((bits & 0x7FFFFFFFu) > 0x7F800000u) bad = true;               // NaN
-        const uint32_t key = sel_fold(bits), hb = key & himask, bin = (key >> shift) & 255u;
+        const uint32_t key = key_of(i, &bad), hb = key & himask, bin = (key >> shift) & 255u;
 #pragma unroll
         for (int t = 0; t < SEL_RANKS; t++)
             if (hb == pfx[t] && (pass || t == 0)) atomicAdd(&h[t * 256 + bin], 1u);
@@ -215,14 +226,27 @@ __global__ void __launch_bounds__(64) k_sel_finish(SelState st, int n_targets, f
     out[t] = sel_lerp(a, b, t ? w1 : w0);
 }
 
-static SelState sel_carve(uint32_t problems, void* base, size_t* bytes)
+static SelState sel_carve(uint32_t problems, const void* base, size_t* bytes)
 {
-    SelState st; char* p = (char*)base;
-    auto take = [&](size_t b) { char* q = p; p += gsr_align(b); return (uint32_t*)q; };
+    SelState st; GsrCarve c(base);
     const size_t P = problems > 0 ? problems : 1;
-    st.prefix = take(P * SEL_RANKS * 4); st.krem = take(P * SEL_RANKS * 4); st.hist = take(P * SEL_RANKS * 256 * 4);
-    *bytes = (size_t)(p - (char*)base);
+    st.prefix = c.take<uint32_t>(P * SEL_RANKS); st.krem = c.take<uint32_t>(P * SEL_RANKS); st.hist = c.take<uint32_t>(P * SEL_RANKS * 256);
+    *bytes = c.bytes();
     return st;
+}
+
+void gsr_select(int kind, const void* values, uint32_t n, const uint32_t* n_dev, const uint32_t rank[4], uint32_t* state, uint32_t* status, hipStream_t s)
+{
+    size_t bytes;
+    const SelState st = sel_carve(1, state, &bytes);      // the prefixes lead: word t of the state ends as the key of rank t
+    static_assert(GSR_SELECT_STATE_BYTES == 2 * 256 + SEL_RANKS * 256 * 4, "one problem's state");
+    const SelRanks r = {{rank[0], rank[1], rank[2], rank[3]}};
+    const uint32_t grid = std::min(gsr_div_up(n, SEL_BLOCK * 8u), 1024u);
+    for (int pass = 0; pass < 4; pass++) {
+        if (kind == GSR_SELECT_FLOAT) hipLaunchKernelGGL(k_sel_hist<SelKeyFloat>, dim3(grid), dim3(SEL_BLOCK), 0, s, SelKeyFloat{(const float*)values}, n, n_dev, st, pass, status);
+        else hipLaunchKernelGGL(k_sel_hist<SelKeyU32Desc>, dim3(grid), dim3(SEL_BLOCK), 0, s, SelKeyU32Desc{(const uint32_t*)values}, n, n_dev, st, pass, status);
+        hipLaunchKernelGGL(k_sel_advance, dim3(1), dim3(SEL_BLOCK), 0, s, st, r, pass, status);
+    }
 }
 
 // ranks {lo0, hi0, lo1, hi1} of up to two targets; false with the error set where one lies outside [0, n)
@@ -257,7 +281,7 @@ extern "C" int gsr_cam_dist_quantiles(const float* points, int64_t N, const floa
     if (!sel_ranks(who, 2, k_lo, k_hi, N, &r)) return 1;
     size_t need;
     const SelState st = sel_carve((uint32_t)C, scratch, &need);
-    if (!scratch || scratch_bytes < need) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, need); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, need, false)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(status_dev, 0, 4, s) || gsr_memset_async(st.hist, 0, (size_t)C * SEL_RANKS * 256 * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
     const uint32_t batches = gsr_div_up((uint32_t)C, CQ_CB);
@@ -290,14 +314,10 @@ extern "C" int gsr_select_lerp(const float* values, int64_t n, const uint32_t* n
     if (!sel_ranks(who, n_targets, k_lo, k_hi, n, &r)) return 1;
     size_t need;
     const SelState st = sel_carve(1, scratch, &need);
-    if (!scratch || scratch_bytes < need) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, need); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, need, false)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    if (gsr_memset_async(status_dev, 0, 4, s) || gsr_memset_async(st.hist, 0, SEL_RANKS * 256 * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
-    const uint32_t grid = std::min(gsr_div_up((uint32_t)n, SEL_BLOCK * 8u), 1024u);
-    for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_sel_hist, dim3(grid), dim3(SEL_BLOCK), 0, s, values, (uint32_t)n, n_dev, st, pass, status_dev);
-        hipLaunchKernelGGL(k_sel_advance, dim3(1), dim3(SEL_BLOCK), 0, s, st, r, pass, status_dev);
-    }
+    if (gsr_memset_async(status_dev, 0, 4, s) || gsr_memset_async(scratch, 0, GSR_SELECT_STATE_BYTES, s)) { gsr_set_error("%s: clear", who); return 1; }
+    gsr_select(GSR_SELECT_FLOAT, values, (uint32_t)n, n_dev, r.k, (uint32_t*)scratch, status_dev, s);
     hipLaunchKernelGGL(k_sel_finish, dim3(1), dim3(64), 0, s, st, n_targets, w[0], w[n_targets > 1 ? 1 : 0], out);
     return gsr_check_launch(who, s, false);
 }
@@ -380,17 +400,16 @@ __global__ void __launch_bounds__(VU_BLOCK) k_vu_emit(VuArgs<T> a, VuLevels lv, 
 }
 
 struct VuScratch { uint32_t *ka, *kb, *va, *vb, *hist, *sums, *map, *heads; uint8_t* flag; size_t bytes; };
-static VuScratch vu_carve(uint32_t N, int32_t L, void* base)
+static VuScratch vu_carve(uint32_t N, int32_t L, const void* base)
 {
-    VuScratch v; char* p = (char*)base;
-    auto take = [&](size_t b) { char* q = p; p += gsr_align(b); return (uint32_t*)q; };
+    VuScratch v; GsrCarve c(base);
     const size_t n = N > 0 ? N : 1;
-    v.ka = take(n * 4); v.kb = take(n * 4); v.va = take(n * 4); v.vb = take(n * 4);
-    v.hist = take(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256) * 4);
-    v.sums = take(((size_t)gsr_div_up((uint32_t)n, 1024u) + 1) * 4);
-    v.map = take(n * 4); v.flag = (uint8_t*)take(n);
-    v.heads = take(n * 4 * (size_t)(L > 0 ? L : 1));
-    v.bytes = (size_t)(p - (char*)base);
+    v.ka = c.take<uint32_t>(n); v.kb = c.take<uint32_t>(n); v.va = c.take<uint32_t>(n); v.vb = c.take<uint32_t>(n);
+    v.hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256));
+    v.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
+    v.map = c.take<uint32_t>(n); v.flag = c.take<uint8_t>(n);
+    v.heads = c.take<uint32_t>(n * (size_t)(L > 0 ? L : 1));
+    v.bytes = c.bytes();
     return v;
 }
 
@@ -445,7 +464,7 @@ extern "C" int gsr_voxel_unique_count(const void* points, int64_t N, int32_t L, 
     if (vu_args(who, points, N, L, init_pos, cell, mode)) return 1;
     if (!record_dev) { gsr_set_error("%s: null record", who); return 1; }
     const VuScratch v = vu_carve((uint32_t)N, L, scratch);
-    if (!scratch || scratch_bytes < v.bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, v.bytes); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, v.bytes, false)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(record_dev, 0, (size_t)(1 + L) * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
     return mode == GSR_VOXEL_F32 ? vu_count<float>(who, points, (uint32_t)N, L, init_pos, cell, v, record_dev, s)
@@ -469,8 +488,8 @@ extern "C" int gsr_voxel_unique_emit(const void* points, int64_t N, int32_t L, c
     if (vu_args(who, points, N, L, init_pos, cell, mode)) return 1;
     if (!record) { gsr_set_error("%s: null record", who); return 1; }
     if (record[0]) { gsr_set_error("%s: the count reported status %u, nothing to emit", who, record[0]); return 1; }
-    const VuScratch v = vu_carve((uint32_t)N, L, const_cast<void*>(scratch));
-    if (!scratch || scratch_bytes < v.bytes) { gsr_set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, v.bytes); return 1; }
+    const VuScratch v = vu_carve((uint32_t)N, L, scratch);
+    if (gsr_scratch_check(who, scratch, scratch_bytes, v.bytes, false)) return 1;
     VuLevels lv;
     lv.L = L;
     uint64_t total = 0;

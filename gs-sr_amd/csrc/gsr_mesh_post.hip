@@ -11,8 +11,8 @@
 //                roots it retries with (at most T rounds).  k_mp_flatten reads the roots off.
 //   numbering    root flags -> exclusive ranks (the keep scan the row compaction uses, gsr_rows_keep_scan) = cluster ids in ascending order of the
 //                smallest triangle; counts by integer atomics, areas by double atomics (wave-aggregated where neighbours share a cluster).
-//   threshold    k-th largest of the C counts: four 8-bit histogram passes (k_mp_hist), every pass re-deriving the prefix from the histograms
-//                before it; k_mp_finish applies the floor.
+//   threshold    k-th largest of the C counts: the radix select of gsr_init.hip (gsr_select, gsr_common.h) over the complemented counts, rank
+//                k - 1, with C read on the device; k_mp_finish applies the floor.
 //   filter       triangle keep flags and vertex-referenced flags (plain byte stores), one keep scan each, then the triangles remapped at their final
 //                places (k_mp_emit) and the vertex rows through the row mover (gsr_rows_move).
 // Termination: probe loops are capped at the table size, find and hook loops by the invariant above; no kernel waits for another workgroup; the
@@ -25,7 +25,6 @@
 
 #define MP_BLOCK 256
 #define MP_EMPTY 0xFFFFFFFFFFFFFFFFull      // no edge has this key: a vertex index is at most 2^31 - 2
-#define MP_HIST_GRID 1024u
 // record words (include/gsrast.h)
 #define MP_R_STATUS 0
 #define MP_R_C 1
@@ -190,49 +189,16 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_label(const int32_t* __restrict
     }
 }
 
-// ---- the k-th largest of counts[0, C): radix select, 8 bits per pass, most significant first
-// after `passes` passes: the high 8 * passes bits of the k-th largest value, and its rank among the values that share them
-__device__ __forceinline__ void mp_select_replay(const uint32_t* hist, int passes, uint32_t k, uint32_t* prefix, uint32_t* k_rem)
-{
-    uint32_t pre = 0, r = k;
-    for (int q = 0; q < passes; q++) {
-        uint32_t cum = 0;
-        for (int b = 255; b >= 0; b--) {
-            const uint32_t n = hist[q * 256 + b];
-            if (cum + n >= r) { pre |= (uint32_t)b << (24 - 8 * q); r -= cum; break; }
-            cum += n;
-        }
-    }
-    *prefix = pre; *k_rem = r;
-}
-__global__ void __launch_bounds__(MP_BLOCK) k_mp_hist(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ record, uint32_t k, int pass, uint32_t* hist)
-{
-    __shared__ uint32_t h[256];
-    __shared__ uint32_t sel;
-    const uint32_t C = record[MP_R_C];
-    if (k < 1u || k > C) return;                  // workgroup-uniform: k_mp_finish reports it
-    h[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) { uint32_t pre, r; mp_select_replay(hist, pass, k, &pre, &r); sel = pre; }
-    __syncthreads();
-    const uint32_t prefix = sel, himask = pass ? ~0u << (32 - 8 * pass) : 0u;
-    const int shift = 24 - 8 * pass;
-    for (uint32_t i = blockIdx.x * MP_BLOCK + threadIdx.x; i < C; i += gridDim.x * MP_BLOCK) {
-        const uint32_t v = counts[i];
-        if ((v & himask) == prefix) atomicAdd(&h[(v >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (h[threadIdx.x]) atomicAdd(hist + pass * 256 + threadIdx.x, h[threadIdx.x]);
-}
 // the fixed words of the record: the threshold (cluster rule) and the counts a scan does not write
-__global__ void __launch_bounds__(64) k_mp_finish(uint32_t* __restrict__ record, const uint32_t* __restrict__ hist, int cluster_rule, uint32_t k, uint32_t floor_,
+__global__ void __launch_bounds__(64) k_mp_finish(uint32_t* __restrict__ record, const uint32_t* __restrict__ sel_state, int cluster_rule, uint32_t k, uint32_t floor_,
                                                   uint32_t V)
 {
     if (threadIdx.x != 0) return;
     uint32_t thr = 0u;
     if (cluster_rule) {
         const uint32_t C = record[MP_R_C];
-        if (k < 1u || k > C) { atomicOr(record + MP_R_STATUS, (uint32_t)GSR_MESH_ERR_KEEP); thr = 0xFFFFFFFFu; }
-        else { uint32_t r; mp_select_replay(hist, 4, k, &thr, &r); thr = max(thr, floor_); }
+        if (k < 1u || k > C) { atomicOr(record + MP_R_STATUS, (uint32_t)GSR_MESH_ERR_KEEP); thr = 0xFFFFFFFFu; }      // the select did not run, or ran beyond the keys
+        else thr = max(~sel_state[0], floor_);        // the key of rank k - 1 is the complement of the k-th largest count
     } else record[MP_R_C] = 0u;
     record[MP_R_THR] = thr;
     record[MP_R_V] = V;                           // overwritten by the vertex scan where unreferenced vertices are dropped
@@ -273,27 +239,26 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_emit(const int32_t* __restrict_
 // ------------------------------------------------------------------------------------------------ C ABI (include/gsrast.h)
 struct MpScratch {
     MpTable tb;
-    uint32_t *parent, *root, *rank, *counts, *sums, *tmap, *hist, *record, *vrank, *vmap;
+    uint32_t *parent, *root, *rank, *counts, *sums, *tmap, *sel, *sel_status, *vrank, *vmap;
     int32_t* clusters;
     uint8_t *tflag, *vflag;
     size_t table_bytes, bytes;
 };
-static MpScratch mp_carve(uint64_t T, uint64_t V, void* base)
+static MpScratch mp_carve(uint64_t T, uint64_t V, const void* base)
 {
-    MpScratch m; char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += gsr_align(bytes); return (void*)q; };
+    MpScratch m; GsrCarve c(base);
     const uint64_t t = T > 0 ? T : 1, n = t > V ? t : V;
     unsigned long long slots = 64;
     while (slots < 2 * 3 * t) slots <<= 1;
     m.tb.mask = slots - 1;
-    m.tb.keys = (unsigned long long*)take(slots * 8); m.tb.owner = (uint32_t*)take(slots * 4);
-    m.table_bytes = (size_t)(p - (char*)base);      // keys and owners are contiguous: one fill with 0xFF
-    m.parent = (uint32_t*)take(t * 4); m.root = (uint32_t*)take(t * 4); m.rank = (uint32_t*)take(t * 4); m.counts = (uint32_t*)take(t * 4);
-    m.clusters = (int32_t*)take(t * 4); m.tmap = (uint32_t*)take(t * 4); m.tflag = (uint8_t*)take(t);
-    m.sums = (uint32_t*)take(((n + 1023) / 1024 + 1) * 4);
-    m.hist = (uint32_t*)take(4 * 256 * 4); m.record = (uint32_t*)take(64);
-    m.vflag = (uint8_t*)take(V); m.vrank = (uint32_t*)take(V * 4); m.vmap = (uint32_t*)take(V * 4);
-    m.bytes = (size_t)(p - (char*)base);
+    m.tb.keys = c.take<unsigned long long>(slots); m.tb.owner = c.take<uint32_t>(slots);
+    m.table_bytes = c.bytes();                      // keys and owners are contiguous: one fill with 0xFF
+    m.parent = c.take<uint32_t>(t); m.root = c.take<uint32_t>(t); m.rank = c.take<uint32_t>(t); m.counts = c.take<uint32_t>(t);
+    m.clusters = c.take<int32_t>(t); m.tmap = c.take<uint32_t>(t); m.tflag = c.take<uint8_t>(t);
+    m.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
+    m.sel_status = c.take<uint32_t>(64); m.sel = c.take<uint32_t>(GSR_SELECT_STATE_BYTES / 4);      // contiguous: one clear; the select's rank-beyond-keys flag stays out of the record
+    m.vflag = c.take<uint8_t>(V); m.vrank = c.take<uint32_t>(V); m.vmap = c.take<uint32_t>(V);
+    m.bytes = c.bytes();
     return m;
 }
 static bool mp_sizes_ok(const char* who, int64_t T, int64_t V)
@@ -334,7 +299,7 @@ extern "C" int gsr_mesh_cluster_triangles(const int32_t* triangles, int64_t n_tr
     if (!status_dev || !scratch || (n_triangles > 0 && (!triangles || !triangle_clusters || !cluster_n_triangles))) { gsr_set_error("%s: null pointer", who); return 1; }
     if (cluster_area && !vertices) { gsr_set_error("%s: the areas need the vertices", who); return 1; }
     const MpScratch m = mp_carve((uint64_t)n_triangles, 0, scratch);
-    if (scratch_bytes < m.bytes || ((uintptr_t)scratch & 15)) { gsr_set_error("%s: scratch of %zu bytes (16-byte aligned) needed, %zu given", who, m.bytes, scratch_bytes); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, m.bytes)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(status_dev, 0, 8, s)) { gsr_set_error("%s: status", who); return 1; }
     if (n_triangles == 0) return gsr_check_launch(who, s, false);
@@ -351,8 +316,8 @@ static int mp_filter_args(const char* who, const gsr_mesh_filter* f, const void*
     if (f->flags & ~(GSR_MESH_DROP_UNREFERENCED | GSR_MESH_DROP_DEGENERATE)) { gsr_set_error("%s: unknown flags %d", who, f->flags); return 1; }
     if (f->remove_mask && f->cluster_to_keep != 0) { gsr_set_error("%s: a remove mask and cluster_to_keep exclude each other", who); return 1; }
     if (f->cluster_to_keep < 0 || f->floor < 0) { gsr_set_error("%s: cluster_to_keep and floor must not be negative", who); return 1; }
-    m = mp_carve((uint64_t)f->n_triangles, (uint64_t)f->n_vertices, const_cast<void*>(scratch));
-    if (scratch_bytes < m.bytes || ((uintptr_t)scratch & 15)) { gsr_set_error("%s: scratch of %zu bytes (16-byte aligned) needed, %zu given", who, m.bytes, scratch_bytes); return 1; }
+    m = mp_carve((uint64_t)f->n_triangles, (uint64_t)f->n_vertices, scratch);
+    if (gsr_scratch_check(who, scratch, scratch_bytes, m.bytes)) return 1;
     return 0;
 }
 
@@ -365,14 +330,16 @@ extern "C" int gsr_mesh_filter_count(const gsr_mesh_filter* f, void* scratch, si
     hipStream_t s = (hipStream_t)stream;
     const uint32_t T = (uint32_t)f->n_triangles, V = (uint32_t)f->n_vertices, g = mp_grid(T);
     const bool rule = f->cluster_to_keep > 0, unref = (f->flags & GSR_MESH_DROP_UNREFERENCED) != 0;
-    if (gsr_memset_async(record_dev, 0, 32, s) || gsr_memset_async(m.hist, 0, 4 * 256 * 4, s) ||
+    if (gsr_memset_async(record_dev, 0, 32, s) ||
         (unref && V > 0 && gsr_memset_async(m.vflag, 0, gsr_align(V, 4), s))) { gsr_set_error("%s: clear", who); return 1; }
     if (rule) {
         if (T > 0 && mp_cluster(who, f->triangles, T, V, nullptr, m, m.clusters, m.counts, nullptr, record_dev + MP_R_STATUS, record_dev + MP_R_C, s)) return 1;
-        for (int pass = 0; pass < 4; pass++)
-            hipLaunchKernelGGL(k_mp_hist, dim3(std::min(g, MP_HIST_GRID)), dim3(MP_BLOCK), 0, s, m.counts, record_dev, (uint32_t)f->cluster_to_keep, pass, m.hist);
+        // a cluster_to_keep beyond the clusters is the device's to report (GSR_MESH_ERR_KEEP): beyond T it cannot be a rank, and the select is left out
+        const uint32_t rank[4] = { (uint32_t)f->cluster_to_keep - 1u, (uint32_t)f->cluster_to_keep - 1u, (uint32_t)f->cluster_to_keep - 1u, (uint32_t)f->cluster_to_keep - 1u };
+        if ((uint32_t)f->cluster_to_keep <= T && gsr_memset_async(m.sel_status, 0, 256 + GSR_SELECT_STATE_BYTES, s)) { gsr_set_error("%s: clear", who); return 1; }
+        if ((uint32_t)f->cluster_to_keep <= T) gsr_select(GSR_SELECT_U32_DESC, m.counts, T, record_dev + MP_R_C, rank, m.sel, m.sel_status, s);
     }
-    hipLaunchKernelGGL(k_mp_finish, dim3(1), dim3(64), 0, s, record_dev, m.hist, rule ? 1 : 0, (uint32_t)f->cluster_to_keep, (uint32_t)f->floor, V);
+    hipLaunchKernelGGL(k_mp_finish, dim3(1), dim3(64), 0, s, record_dev, m.sel, rule ? 1 : 0, (uint32_t)f->cluster_to_keep, (uint32_t)f->floor, V);
     hipLaunchKernelGGL(k_mp_keep, dim3(g), dim3(MP_BLOCK), 0, s, f->triangles, T, V, f->remove_mask, rule ? m.clusters : nullptr, m.counts, record_dev, f->flags, m.tflag,
                        m.vflag);
     gsr_rows_keep_scan(m.tflag, T, m.sums, m.tmap, nullptr, record_dev + MP_R_T, s);

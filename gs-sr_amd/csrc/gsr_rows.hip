@@ -1,9 +1,10 @@
-// gsr_rows.hip -- the row mover (gsr_common.h gsr_rows_move): one destination-driven copy kernel behind gsr_rows_compact_multi (gsr_anchor.hip) and
-// gsr_densify_emit (gsr_densify.hip).  Output row r of every tensor of a table is src row map[r], zeros, or a row of the tensor's tail.
+// gsr_rows.hip -- the row mover (gsr_common.h gsr_rows_move): one destination-driven copy kernel behind gsr_rows_compact_multi (below),
+// gsr_densify_emit (gsr_densify.hip) and gsr_mesh_filter_emit (gsr_mesh_post.hip); and the keep scan that drives it (gsr_rows_keep_scan).  Output row r of every tensor of a table is src row map[r], zeros, or a row of the tensor's tail.
 //
 // Destination-driven because densify needs it (a split parent has several output rows: a scatter cannot serve) and because it writes whole
 // lines: a lane owns one unit of consecutive output bytes, reads are contiguous over every run of surviving rows.
-#include "gsr_common.h"
+#include "gsr_compact.h"
+#include <vector>
 
 #define ROWS_MAX_T 24               // tensors per launch: the table travels in the kernel arguments
 #define ROWS_CHUNK 2048             // copy units per block of 256 threads
@@ -102,4 +103,51 @@ int gsr_rows_move(const char* who, const gsr_rows_map& m, int32_t count, const g
         if (blocks) hipLaunchKernelGGL(k_rows_move, dim3((uint32_t)blocks), dim3(256), 0, s, T, m.map, m.n_map_dev);
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rows: compact + append
+// dst = [src[keep] ; tail] for many tensors that share one keep mask over N rows (the reference's per-tensor x[mask] + cat over six parameters,
+// twelve Adam moments and four accumulators: ~60 launches and a nonzero() synchronisation each).  The keep -> position scan runs once and leaves
+// map[position] = row for every kept row; the row mover does the rest, with the number kept read on the device.
+struct RowsKeepOp {
+    const uint8_t* mask; uint32_t *map, *rank;
+    __device__ bool keep(uint32_t i) const { return mask[i] != 0; }
+    __device__ void place(uint32_t i, uint32_t p) const { if (map) map[p] = i; if (rank) rank[i] = p; }      // p <= i < N
+};
+void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_t* map, uint32_t* rank, uint32_t* count_dev, hipStream_t s)
+{
+    gsr_compact(RowsKeepOp{keep, map, rank}, N, sums, count_dev, s);
+}
+
+struct RowsScratch { uint32_t *sums, *map, *count; size_t bytes; };
+static RowsScratch rows_carve(uint32_t N, const void* base)
+{
+    RowsScratch r; GsrCarve c(base);
+    const size_t n = N > 0 ? N : 1;
+    r.sums = c.take<uint32_t>(gsr_compact_sums_words(n)); r.map = c.take<uint32_t>(n); r.count = c.take<uint32_t>(16);
+    r.bytes = c.bytes();
+    return r;
+}
+extern "C" size_t gsr_rows_compact_scratch_bytes(int64_t N)
+{
+    if (N < 0 || N >= (1ll << 31)) return 0;
+    return rows_carve((uint32_t)N, nullptr).bytes;
+}
+
+extern "C" int gsr_rows_compact_multi(int64_t N, const uint8_t* keep, int32_t count, const gsr_rows_tensor* t, void* scratch, size_t scratch_bytes,
+                                      void* stream)
+{
+    const char* who = "rows_compact_multi";
+    if (N < 0 || N >= (1ll << 31)) { gsr_set_error("%s: N=%lld out of range", who, (long long)N); return 1; }
+    if (N > 0 && !keep) { gsr_set_error("%s: keep is NULL", who); return 1; }
+    const RowsScratch r = rows_carve((uint32_t)N, scratch);
+    if (gsr_scratch_check(who, scratch, scratch_bytes, r.bytes, false)) return 1;
+    std::vector<gsr_rows_item> items;
+    for (int32_t i = 0; t && i < count; i++) items.push_back({t[i].src, t[i].dst, t[i].tail, t[i].row_bytes, t[i].n_tail, false});
+    const gsr_rows_map m = {r.map, r.count, (uint32_t)N, 0u, (uint32_t)N};
+    hipStream_t s = (hipStream_t)stream;
+    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, false, s)) return 1;                      // the checks, before anything is launched
+    gsr_rows_keep_scan(keep, (uint32_t)N, r.sums, r.map, nullptr, r.count, s);
+    if (gsr_rows_move(who, m, count, t ? items.data() : nullptr, true, s)) return 1;
+    return gsr_check_launch(who, s, false);
 }

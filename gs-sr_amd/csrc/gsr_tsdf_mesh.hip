@@ -18,8 +18,7 @@
 #include "gsr_tsdf_view.h"
 #include "gsr_scan.h"
 #include <algorithm>
-#define GSR_MC_TABLE_QUAL static __constant__ const
-#include "gsr_mc_table.h"
+#include "gsr_mc.h"
 
 #define TM_H 18                          // staged edge: the unit and one voxel on either side
 #define TM_HV (TM_H * TM_H * TM_H)
@@ -70,7 +69,7 @@ __device__ __forceinline__ void tm_stage(const SparseTsdf& v, TmShared& S, int b
         }
         S.nb[tid] = nb;
     }
-    reinterpret_cast<uint4*>(&S.tab[0][0])[tid] = reinterpret_cast<const uint4*>(&GSR_MC_TABLE[0][0])[tid];
+    mc_stage_table(S.tab);
     // the unit itself: its weight and tsdf planes in brick order, 16 bytes per lane (the lanes of a wave read 1 KB per plane); a clear bit loads nothing
     {
         const TsLane L = ts_lane(tid);
@@ -126,12 +125,9 @@ __device__ __forceinline__ void tm_stage(const SparseTsdf& v, TmShared& S, int b
 __device__ __forceinline__ int tm_case(const TmShared& S, int x, int y, int z)
 {
     const int h = tm_h(x, y, z);
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) c |= (S.f[h + (i & 1) * TM_H * TM_H + ((i >> 1) & 1) * TM_H + ((i >> 2) & 1)] < 0.f ? 1 : 0) << i;
-    return c;
+    return mc_case([&](int i) { return S.f[h + (i & 1) * TM_H * TM_H + ((i >> 1) & 1) * TM_H + ((i >> 2) & 1)]; });
 }
-__device__ __forceinline__ uint32_t tm_tris(const TmShared& S, int c) { return S.tab[c][3] >> 24; }
+__device__ __forceinline__ uint32_t tm_tris(const TmShared& S, int c) { return mc_tris(S.tab, c); }
 
 // row (x, y): which of its 48 edges carry a vertex, and how many triangles its 16 cubes emit
 __device__ __forceinline__ unsigned long long tm_row(const TmShared& S, int x, int y, uint32_t* ntri)
@@ -181,19 +177,10 @@ __global__ void __launch_bounds__(256) k_tm_count(SparseTsdf v, TmArgs a)
 __global__ void __launch_bounds__(1024) k_tm_scan(TmArgs a)
 {
     __shared__ uint32_t lds[17];
-    for (int arr = 0; arr < 2; arr++) {
-        uint32_t* d = a.base + (size_t)arr * a.n;
-        unsigned long long run = 0ull;
-        for (int i0 = 0; i0 < a.n; i0 += 1024) {
-            const int i = i0 + (int)threadIdx.x;
-            const uint32_t c = i < a.n ? d[i] : 0u;
-            uint32_t tot = 0;
-            const uint32_t ex = block_excl_scan(c, lds, &tot);
-            if (i < a.n) d[i] = (uint32_t)(run + ex);      // wraps only if the total does not fit either: the host refuses such a mesh
-            run += tot;
-        }
-        if (threadIdx.x == 0) a.totals[arr] = run;
-    }
+    uint32_t* const d[2] = { a.base, a.base + a.n };
+    unsigned long long total[2] = { 0ull, 0ull };
+    block_scan_arrays<1024, 2>(d, (uint32_t)a.n, lds, total);      // an entry wraps only if the total does not fit either: the host refuses such a mesh
+    if (threadIdx.x == 0) { a.totals[0] = total[0]; a.totals[1] = total[1]; }
 }
 
 // the colour of voxel (lx, ly, lz) in [0, 16]^3 of the staged unit (16 = the next unit)
@@ -259,7 +246,7 @@ __global__ void __launch_bounds__(256) k_tm_emit(SparseTsdf v, TmArgs a, float* 
                 for (int ax = 0; ax < 3; ax++) {
                     if (!((eb >> ax) & 1u)) continue;
                     const float f1 = S.f[h + (ax == 0 ? TM_H * TM_H : ax == 1 ? TM_H : 1)];
-                    const float t = f0 / (f0 - f1);
+                    const float t = mc_cross(f0, f1);
                     float c1[3];
                     tm_color(v, S, x + (ax == 0), y + (ax == 1), z + (ax == 2), c1);
                     const int g = ax == 0 ? gx : ax == 1 ? gy : gz0 + z;
@@ -275,44 +262,34 @@ __global__ void __launch_bounds__(256) k_tm_emit(SparseTsdf v, TmArgs a, float* 
                 }
             }
             if (!S.cv[tm_c(x, y, z)]) continue;
-            const int c = tm_case(S, x, y, z);
-            const uint32_t ntri = tm_tris(S, c);
-            const uint8_t* e = reinterpret_cast<const uint8_t*>(&S.tab[c][0]);
-            for (uint32_t j = 0; j < ntri; j++, ti++) {
-                int32_t idx[3];
-#pragma unroll
-                for (int q = 0; q < 3; q++) {
-                    const int ed = e[3 * j + q], cn = GSR_MC_EDGE_CORNER[ed];
-                    idx[q] = (int32_t)tm_vertex(a, S, x + (cn & 1), y + ((cn >> 1) & 1), z + ((cn >> 2) & 1), GSR_MC_EDGE_AXIS[ed]);
-                }
-                if (ti < tott) { tris[3 * ti] = idx[0]; tris[3 * ti + 1] = idx[1]; tris[3 * ti + 2] = idx[2]; }
-            }
+            ti = mc_triangles(S.tab, tm_case(S, x, y, z), ti, tott, tris,
+                              [&](int cn, int axis) { return tm_vertex(a, S, x + (cn & 1), y + ((cn >> 1) & 1), z + ((cn >> 2) & 1), axis); });
         }
         __syncthreads();      // the next unit's staging overwrites what slower threads still read
     }
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/gsrast.h)
-static size_t tm_off_inv(size_t n) { return gsr_align(n * TM_ROWS * sizeof(unsigned long long)); }
-static size_t tm_off_base(size_t n) { return tm_off_inv(n) + gsr_align(n * sizeof(int32_t)); }
-static size_t tm_off_totals(size_t n) { return tm_off_base(n) + gsr_align(2 * n * sizeof(uint32_t)); }
+// fills the scratch pointers of `a` for n units; returns the bytes
+static size_t tm_carve(TmArgs& a, size_t n, const void* base)
+{
+    GsrCarve c(base);
+    a.rows = c.take<unsigned long long>(n * TM_ROWS); a.inv = c.take<int32_t>(n); a.base = c.take<uint32_t>(2 * n); a.totals = c.take<unsigned long long>(2);
+    return c.bytes();
+}
 extern "C" size_t gsr_tsdf_sparse_mesh_scratch_bytes(int32_t n_units)
 {
-    return n_units > 0 ? tm_off_totals((size_t)n_units) + 256 : 256;
+    TmArgs a;
+    return tm_carve(a, n_units > 0 ? (size_t)n_units : 0, nullptr);
 }
 static int tm_args(const char* who, const gsr_tsdf_sparse* s, int32_t n_units, const int32_t* order, float min_weight, void* scratch, size_t scratch_bytes, TmArgs& a)
 {
     if (check_vol(s)) return 1;
     if (n_units <= 0 || (uint32_t)n_units > s->cap_blocks) { gsr_set_error("%s: %d units do not fit the volume", who, n_units); return 1; }
     if (!order || !scratch) { gsr_set_error("%s: null unit order / scratch", who); return 1; }
-    if (scratch_bytes < gsr_tsdf_sparse_mesh_scratch_bytes(n_units) || ((uintptr_t)scratch & 15)) {
-        gsr_set_error("%s: scratch of %zu bytes (16-byte aligned) needed, %zu given", who, gsr_tsdf_sparse_mesh_scratch_bytes(n_units), scratch_bytes); return 1;
-    }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, tm_carve(a, (size_t)n_units, scratch))) return 1;
     if (!(min_weight == min_weight)) { gsr_set_error("%s: min_weight is not a number", who); return 1; }
-    char* p = (char*)scratch;
-    const size_t n = (size_t)n_units;
-    a.order = order; a.rows = (unsigned long long*)p; a.inv = (int32_t*)(p + tm_off_inv(n)); a.base = (uint32_t*)(p + tm_off_base(n));
-    a.totals = (unsigned long long*)(p + tm_off_totals(n)); a.n = n_units; a.min_weight = min_weight; a.vl = s->voxel_length;
+    a.order = order; a.n = n_units; a.min_weight = min_weight; a.vl = s->voxel_length;
     return 0;
 }
 extern "C" int gsr_tsdf_sparse_mesh_count(const gsr_tsdf_sparse* s, int32_t n_units, const int32_t* order, float min_weight, void* scratch, size_t scratch_bytes,

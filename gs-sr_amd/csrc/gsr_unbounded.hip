@@ -12,8 +12,7 @@
 #include "gsr_scan.h"
 #include "gsr_tsdf_point.h"
 #include <algorithm>
-#define GSR_MC_TABLE_QUAL static __constant__ const
-#include "gsr_mc_table.h"
+#include "gsr_mc.h"
 
 struct UbFrame {
     float cx, cy, cz, radius, voxel;
@@ -139,10 +138,7 @@ __device__ __forceinline__ int ub_case(const UbMc& m, int64_t i, int p, int gy, 
 {
     if (p >= m.own || p + 1 >= m.np || gy + 1 >= m.ny || gz + 1 >= m.nz) return -1;
     const int64_t sx = (int64_t)m.ny * m.nz;
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c |= (m.f[i + (k & 1) * sx + ((k >> 1) & 1) * (int64_t)m.nz + ((k >> 2) & 1)] < 0.f ? 1 : 0) << k;
-    return c;
+    return mc_case([&](int k) { return m.f[i + (k & 1) * sx + ((k >> 1) & 1) * (int64_t)m.nz + ((k >> 2) & 1)]; });
 }
 __device__ __forceinline__ void ub_place(const UbMc& m, int64_t i, int& p, int& gy, int& gz)
 {
@@ -161,7 +157,7 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_mc_count(UbMc m)
         ub_place(m, i, p, gy, gz);
         e = ub_edges(m, i, p, gy, gz);
         const int c = ub_case(m, i, p, gy, gz);
-        if (c >= 0) nt = GSR_MC_TABLE[c][15];
+        if (c >= 0) nt = mc_tris_const(c);
     }
     uint32_t totv = 0, tott = 0;
     const uint32_t pv = block_excl_scan((uint32_t)__popc(e), scan, &totv);
@@ -174,22 +170,15 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_mc_count(UbMc m)
 __global__ void __launch_bounds__(1024) k_ub_mc_scan(UbMc m)
 {
     __shared__ uint32_t lds[17];
-    const uint32_t b0 = (uint32_t)(m.P0 / UB_BLOCK);      // the workgroup of the first point that is not owned (P0 < M)
-    unsigned long long runv = 0ull, runt = 0ull;
-    for (uint32_t j0 = 0; j0 < m.nb; j0 += 1024) {
-        const uint32_t j = j0 + threadIdx.x;
-        const uint32_t cv = j < m.nb ? m.vsum[j] : 0u, ct = j < m.nb ? m.tsum[j] : 0u;
-        uint32_t totv = 0, tott = 0;
-        const uint32_t ev = block_excl_scan(cv, lds, &totv), et = block_excl_scan(ct, lds, &tott);
-        if (j < m.nb) {
-            m.vsum[j] = (uint32_t)(runv + ev); m.tsum[j] = (uint32_t)(runt + et);      // fit: the host refuses slabs of more than (2^31 - 1) / 5 points
-            if (m.P0 < m.M && j == b0) m.totals[0] = runv + ev + ((m.word[m.P0] >> UB_T_BITS) & ((1u << UB_V_BITS) - 1u));
-        }
-        runv += totv; runt += tott;
-    }
+    uint32_t* const d[2] = { m.vsum, m.tsum };
+    unsigned long long total[2] = { 0ull, 0ull };
+    block_scan_arrays<1024, 2>(d, m.nb, lds, total);      // the prefixes fit: the host refuses slabs of more than (2^31 - 1) / 5 points
+    // the vertices in front of P0, the first point that is not owned: its workgroup's prefix, read by the thread that stored it, + its own place in the workgroup
+    const uint32_t b0 = (uint32_t)(m.P0 / UB_BLOCK);
+    if (m.P0 < m.M && threadIdx.x == b0 % 1024u) m.totals[0] = (unsigned long long)m.vsum[b0] + ((m.word[m.P0] >> UB_T_BITS) & ((1u << UB_V_BITS) - 1u));
     if (threadIdx.x == 0) {
-        if (m.P0 >= m.M) m.totals[0] = runv;
-        m.totals[1] = runt;
+        if (m.P0 >= m.M) m.totals[0] = total[0];
+        m.totals[1] = total[1];
     }
 }
 
@@ -204,7 +193,7 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_mc_emit(UbMc m, UbAxes a, int64
                                                          int32_t* __restrict__ tris)
 {
     __shared__ uint32_t tab[256][4];
-    reinterpret_cast<uint4*>(&tab[0][0])[threadIdx.x] = reinterpret_cast<const uint4*>(&GSR_MC_TABLE[0][0])[threadIdx.x];
+    mc_stage_table(tab);
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * UB_BLOCK + threadIdx.x;
     if (i >= m.P0 || i >= m.M) return;
@@ -219,7 +208,7 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_mc_emit(UbMc m, UbAxes a, int64
         for (int ax = 0; ax < 3; ax++) {
             if (!((e >> ax) & 1u)) continue;
             const float f1 = m.f[i + (ax == 0 ? (int64_t)m.ny * m.nz : ax == 1 ? (int64_t)m.nz : 1)];
-            const float t = f0 / (f0 - f1);
+            const float t = mc_cross(f0, f1);
             const float lo = q[ax], hi = ax == 0 ? a.xs[p + 1] : ax == 1 ? a.ys[gy + 1] : a.zs[gz + 1];
             float o[3] = { q[0], q[1], q[2] };
             o[ax] = lo + t * (hi - lo);
@@ -229,20 +218,10 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_mc_emit(UbMc m, UbAxes a, int64
     }
     const int c = ub_case(m, i, p, gy, gz);
     if (c < 0) return;
-    const uint32_t ntri = tab[c][3] >> 24;
-    if (!ntri) return;
-    const uint8_t* ed = reinterpret_cast<const uint8_t*>(&tab[c][0]);
     const int64_t sx = (int64_t)m.ny * m.nz;
-    int64_t ti = (int64_t)m.tsum[blockIdx.x] + (w & ((1u << UB_T_BITS) - 1u));
-    for (uint32_t j = 0; j < ntri; j++, ti++) {
-        int32_t idx[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int en = ed[3 * j + k], cn = GSR_MC_EDGE_CORNER[en];
-            idx[k] = (int32_t)(vbase + ub_vertex(m, i + (cn & 1) * sx + ((cn >> 1) & 1) * (int64_t)m.nz + ((cn >> 2) & 1), GSR_MC_EDGE_AXIS[en]));
-        }
-        if (ti < nt) { tris[3 * ti] = idx[0]; tris[3 * ti + 1] = idx[1]; tris[3 * ti + 2] = idx[2]; }
-    }
+    mc_triangles(tab, c, (int64_t)m.tsum[blockIdx.x] + (w & ((1u << UB_T_BITS) - 1u)), nt, tris, [&](int cn, int axis) {
+        return vbase + ub_vertex(m, i + (cn & 1) * sx + ((cn >> 1) & 1) * (int64_t)m.nz + ((cn >> 2) & 1), axis);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ finish / texture
@@ -336,13 +315,18 @@ extern "C" int gsr_unbounded_lattice_tsdf(int32_t nx, int32_t ny, int32_t nz, co
 }
 
 static int64_t ub_numbered(int32_t np, int32_t ny, int32_t nz, int32_t own) { return (int64_t)std::min(own + 1, np) * ny * nz; }
-static size_t ub_off_vsum(int64_t M) { return gsr_align((size_t)M * sizeof(uint32_t)); }
-static size_t ub_off_tsum(int64_t M) { return ub_off_vsum(M) + gsr_align((size_t)((M + UB_BLOCK - 1) / UB_BLOCK) * sizeof(uint32_t)); }
-static size_t ub_off_totals(int64_t M) { return ub_off_tsum(M) + gsr_align((size_t)((M + UB_BLOCK - 1) / UB_BLOCK) * sizeof(uint32_t)); }
+// fills the scratch pointers of `m` for M numbered points; returns the bytes
+static size_t ub_carve(UbMc& m, int64_t M, const void* base)
+{
+    GsrCarve c(base);
+    const size_t nb = (size_t)((M + UB_BLOCK - 1) / UB_BLOCK);      // workgroups
+    m.word = c.take<uint32_t>((size_t)M); m.vsum = c.take<uint32_t>(nb); m.tsum = c.take<uint32_t>(nb); m.totals = c.take<unsigned long long>(2);
+    return c.bytes();
+}
 extern "C" size_t gsr_unbounded_mc_scratch_bytes(int32_t np, int32_t ny, int32_t nz)
 {
-    if (np < 1 || ny < 1 || nz < 1) return 256;
-    return ub_off_totals((int64_t)np * ny * nz) + 256;
+    UbMc m;
+    return ub_carve(m, (np < 1 || ny < 1 || nz < 1) ? 0 : (int64_t)np * ny * nz, nullptr);
 }
 static int ub_mc(const char* who, int32_t np, int32_t ny, int32_t nz, int32_t own, const float* f, const void* scratch, size_t scratch_bytes, UbMc& m)
 {
@@ -353,13 +337,9 @@ static int ub_mc(const char* who, int32_t np, int32_t ny, int32_t nz, int32_t ow
     if (!f || !scratch) { gsr_set_error("%s: null pointer (tsdf / scratch)", who); return 1; }
     const int64_t M = ub_numbered(np, ny, nz, own);
     if (M > UB_MAX_POINTS) { gsr_set_error("%s: %lld points in one slab, at most %lld: use a smaller slab", who, (long long)M, (long long)UB_MAX_POINTS); return 1; }
-    if (scratch_bytes < gsr_unbounded_mc_scratch_bytes(np, ny, nz) || ((uintptr_t)scratch & 15)) {
-        gsr_set_error("%s: scratch of %zu bytes (16-byte aligned) needed, %zu given", who, gsr_unbounded_mc_scratch_bytes(np, ny, nz), scratch_bytes); return 1;
-    }
-    char* p = (char*)scratch;
-    m.f = f; m.word = (uint32_t*)p; m.vsum = (uint32_t*)(p + ub_off_vsum(M)); m.tsum = (uint32_t*)(p + ub_off_tsum(M));
-    m.totals = (unsigned long long*)(p + ub_off_totals(M));
-    m.M = M; m.P0 = (int64_t)own * ny * nz; m.np = np; m.ny = ny; m.nz = nz; m.own = own; m.nb = (uint32_t)((M + UB_BLOCK - 1) / UB_BLOCK);
+    if (gsr_scratch_check(who, scratch, scratch_bytes, gsr_unbounded_mc_scratch_bytes(np, ny, nz))) return 1;      // a slab's size, whatever it owns
+    ub_carve(m, M, scratch);
+    m.f = f; m.M = M; m.P0 = (int64_t)own * ny * nz; m.np = np; m.ny = ny; m.nz = nz; m.own = own; m.nb = (uint32_t)((M + UB_BLOCK - 1) / UB_BLOCK);
     return 0;
 }
 

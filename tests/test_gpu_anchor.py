@@ -98,7 +98,9 @@ def cell_order_keys(a, origin, cell):
     return (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
 
 
-@pytest.mark.parametrize("N,k,F", [(300000, 10, 32), (77777, 3, 5)])
+# the last four: N * (1 + k) = 1023, 1024, 1025 and 2049 entries in the first level -- a last workgroup of the compaction one short, exactly full, one
+# over, and a third workgroup that holds one entry
+@pytest.mark.parametrize("N,k,F", [(300000, 10, 32), (77777, 3, 5), (341, 2, 5), (512, 1, 5), (205, 4, 5), (683, 2, 5)])
 def test_anchor_growing_equals_restatement(N, k, F):
     from gsrast import anchors
     vs = 0.01

@@ -112,6 +112,30 @@ def test_random_field_min_weight():
     _check(vol.extract_triangle_mesh(), ref.extract(T, W, Cc, VL, origin=org), "min_weight 0")
 
 
+def test_more_than_1024_units():
+    """1030 units in a row along x: the one-workgroup scan of the units' vertex and triangle counts takes a second chunk of 1024 and carries the
+    first chunk's totals into it.  A random field in the units at output positions 0, 1, 1023, 1024, 1028 and 1029 -- either side of the chunk
+    edge and at both ends; the others hold tsdf 0.5 at weight 1: present, live, without a surface of their own, but with one against a field
+    unit beside them.  Inserted in a shuffled order, so that a unit's place in the pool is not its place in the output."""
+    rng = np.random.default_rng(13)
+    n = 1030
+    f = np.full((16 * n, 16, 16), 0.5, np.float32); w = np.ones_like(f); col = np.zeros(f.shape + (3,), np.float32)
+    for u in (0, 1, 1023, 1024, 1028, 1029):
+        s = slice(16 * u, 16 * u + 16)
+        f[s] = rng.uniform(-1, 1, (16, 16, 16)).astype(np.float32)
+        f[s][rng.uniform(size=(16, 16, 16)) < 0.01] = 0.0
+        w[s] = ((rng.uniform(size=(16, 16, 16)) > 0.1) * rng.integers(1, 9, (16, 16, 16))).astype(np.float32)
+        col[s] = rng.uniform(0, 255, (16, 16, 16, 3)).astype(np.float32)
+    want = ref.extract(f, w, col, VL)
+    units = ref.units_from_dense(f, w, col, (0, 0, 0))
+    assert len(units[0]) == n > 1024 and units[0][1024].tolist() == [1024, 0, 0]
+    in_late_units = want[0][:, 0] > VL * 16 * 1024                # vertices of the units of the second chunk
+    assert in_late_units.sum() > 1000 and (~in_late_units).sum() > 1000
+    vol = _volume(units, cap=2048, perm=rng.permutation(n))
+    assert vol.num_units == n
+    _check(vol.extract_triangle_mesh(), want, "1030 units")
+
+
 def test_sphere_on_the_device():
     n, h, centre, r = 32, 0.05, (0.8131, 0.7877, 0.8023), 0.41
     tsdf, w, col = ref.sphere(n, h, centre, r)

@@ -128,6 +128,36 @@ def test_threshold_matrix(k):
     assert sorted(cn.tolist()) == sorted(cases.MATRIX[k][1])
 
 
+SELECT_SIZES = [1, 2, 255, 256, 257, 65536, 65537]
+
+
+@functools.lru_cache(maxsize=None)
+def _select_mesh():
+    return cases.clusters_mesh(SELECT_SIZES, seed=5, shuffle=True, spare_vertices=2)
+
+
+def test_select_decided_in_every_byte(monkeypatch):
+    """Seven strips whose sizes part in different passes of the radix select of the k-th largest count: 1, 2 and 255 share everything but the lowest
+    byte, 256 and 257 are told from them by the second byte and from each other by the lowest, 65536 and 65537 by the third and the lowest (a top
+    byte other than 0 would take 2^24 triangles).  Every k from 1 to 7 through post_process_mesh, where the floor of 50 hides the thresholds 1 and 2;
+    and with the floor at 0, in the restatement and in the filter, so that each of the seven thresholds is the one applied."""
+    from gsrast import mesh
+    v, c, t = _select_mesh()
+    for k in range(1, 8):
+        _check_post(v, c, t, k)
+    with pytest.raises(IndexError, match="index -8 is out of bounds for axis 0 with size 7"):
+        mesh.post_process_mesh(_mesh(v, c, t), 8)
+    monkeypatch.setattr(mesh, "FLOOR", 0)
+    monkeypatch.setattr(ref, "FLOOR", 0)
+    m = _mesh(v, c, t)
+    for k in range(1, 8):
+        want = ref.post_process_mesh(v, c, t, cluster_to_keep=k)[:3]
+        nv, nc, tris, rec = mesh._filter(m, cluster_to_keep=k, flags=mesh.DROP_UNREFERENCED | mesh.DROP_DEGENERATE)
+        assert rec[:3] == [0, 7, sorted(SELECT_SIZES)[-k]], (k, rec)
+        assert tuple(x.cpu().numpy().tobytes() for x in (nv, nc, tris)) == tuple(np.ascontiguousarray(a).tobytes() for a in want), k
+        assert int(tris.shape[0]) == sum(n for n in SELECT_SIZES if n >= sorted(SELECT_SIZES)[-k])
+
+
 def test_errors():
     from gsrast import mesh
     v, c, t = _matrix_mesh()

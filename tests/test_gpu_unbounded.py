@@ -157,6 +157,28 @@ def test_marching_cubes_equals_the_restatement(name):
         assert t.cpu().numpy().tobytes() == wt.tobytes(), slab
 
 
+def test_marching_cubes_scans_more_than_1024_workgroups():
+    """A 68 x 64 x 64 lattice: a plane is 16 workgroups of 256 points, so the one-workgroup scan over the workgroups' sums takes a second chunk of
+    1024 and carries the first chunk's total into it.  One slab: 1088 workgroups.  slab=66: the first slab owns 65 planes, and its first point
+    that is not owned, whose prefix is the slab's vertex count, lies in workgroup 1040, past the first chunk.  slab=64: exactly 1024 workgroups."""
+    from gsrast.unbounded import lattice_marching_cubes, slab_plan
+    rng = np.random.default_rng(5)
+    axes = tuple(np.cumsum(rng.uniform(0.03, 0.06, n)).astype(np.float32) - np.float32(0.045 * n / 2) for n in (68, 64, 64))
+    f = sphere_field(axes, centre=(0.1, -0.05, 0.02), r=1.38)
+    groups = lambda slab: [(min(own + 1, planes) * 64 * 64 // 256, own * 64 * 64 // 256) for _, own, planes in slab_plan(68, slab)]
+    assert groups(None) == [(1088, 1088)]
+    assert groups(66)[0] == (1056, 1040) and groups(64)[0] == (1024, 1008)
+    wv, wt = ref.marching_cubes(f, *axes)
+    gx = np.searchsorted(axes[0], wv[:, 0], side="right") - 1
+    assert len(wv) > 10000 and gx.min() < 10 and (gx >= 65).sum() > 100      # the surface has vertices in the workgroups of both chunks: planes up to 63, and 64 on
+    ft = torch.from_numpy(f).cuda()
+    for slab in (None, 66, 64):
+        v, t = lattice_marching_cubes(ft, *axes, slab=slab)
+        assert v.shape == (len(wv), 3) and t.shape == (len(wt), 3), (slab, v.shape, t.shape)
+        assert v.cpu().numpy().tobytes() == wv.tobytes(), slab
+        assert t.cpu().numpy().tobytes() == wt.tobytes(), slab
+
+
 @pytest.mark.parametrize("V", [1, 5, 3000])
 def test_texture_equals_the_per_frame_chain(V):
     from gsrast.unbounded import texture_vertices

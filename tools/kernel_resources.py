@@ -9,7 +9,9 @@ SRC = os.path.join(ROOT, "gs-sr_amd", "csrc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "--cuda-device-only", "-S"]
 PRE = ["-ffp-contract=off"]
 BLEND = ["-ffp-contract=fast", "-fno-slp-vectorize"]
-FLAGS = {"gsr_preprocess.hip": PRE, "gsr_extra.hip": PRE, "gsr_mvloss.hip": PRE, "gsr_tsdf_sparse.hip": PRE, "gsr_blend.hip": BLEND, "gsr_blend_sp.hip": BLEND}
+# the units the Makefile builds with PRE_FLAGS and with BLEND_FLAGS; every other unit gets COMMON alone
+FLAGS = {f"gsr_{u}.hip": PRE for u in ("preprocess", "extra", "binning", "mvloss", "tsdf_sparse", "tsdf_mesh", "unbounded", "mesh_post", "anchor", "densify", "init")}
+FLAGS.update({"gsr_blend.hip": BLEND, "gsr_blend_sp.hip": BLEND})
 
 
 def demangle(names):
@@ -42,7 +44,7 @@ def main():
             vg, sg, sp, lds = int(g("vgpr_count") or 0), int(g("sgpr_count") or 0), int(g("vgpr_spill_count") or 0), int(g("group_segment_fixed_size") or 0)
             ag = int(g("agpr_count") or 0)
             alloc = -(-(vg + ag) // 8) * 8
-            rows.append((name, dict(vgpr=vg, agpr=ag, sgpr=sg, vgpr_spills=sp, lds_bytes=lds, max_threads=int(g("max_flat_workgroup_size") or 0),
+            rows.append((name, dict(vgpr=vg, agpr=ag, sgpr=sg, vgpr_spills=sp, scratch_bytes=int(g("private_segment_fixed_size") or 0), lds_bytes=lds, max_threads=int(g("max_flat_workgroup_size") or 0),
                                     waves_per_simd_by_vgpr=min(8, 512 // max(alloc, 8)),
                                     workgroups_per_cu_by_lds=(163840 // lds) if lds else None)))
         for (n, row), dn in zip(rows, demangle([n for n, _ in rows])):
