@@ -418,7 +418,11 @@ __global__ void __launch_bounds__(256) k_ts_rehash(SparseTsdf v, int n)
 __global__ void __launch_bounds__(256) k_ts_insert_list(SparseTsdf v, const int32_t* __restrict__ coords, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) (void)ts_insert(v, coords[3 * i], coords[3 * i + 1], coords[3 * i + 2]);
+    if (i >= n) return;
+    const int x = coords[3 * i], y = coords[3 * i + 1], z = coords[3 * i + 2];
+    // outside the 21-bit key range the packed key would be another unit's (or the empty key): the "out of range" flag of the touch pass, never a silent alias
+    if (min(x, min(y, z)) < -(1 << 20) + 1 || max(x, max(y, z)) > (1 << 20) - 2) { v.counters[3] = 1; return; }
+    (void)ts_insert(v, x, y, z);
 }
 // self <- weighted merge of self and the given units (tsdf, weight, colour per unit): the running averages are associative in
 // (sum w*tsdf, sum w), so fusing per-tile volumes equals integrating all frames into one volume up to fp32 rounding.
@@ -582,10 +586,15 @@ extern "C" int gsr_tsdf_sparse_rehash(const gsr_tsdf_sparse* s, int32_t n_units,
 static int merge_insert(const gsr_tsdf_sparse* s, SparseTsdf& v, const int32_t* coords, int32_t n_units, hipStream_t st)
 {
     hipLaunchKernelGGL(k_ts_insert_list, dim3((n_units + 255) / 256), dim3(256), 0, st, v, coords, n_units);
-    int32_t c[3] = { 0, 0, 0 };
+    int32_t c[4] = { 0, 0, 0, 0 };
     GSR_CHECK(hipMemcpyAsync(c, v.counters, sizeof(c), hipMemcpyDeviceToHost, st), "tsdf_sparse: read counters");
     GSR_CHECK(hipStreamSynchronize(st), "tsdf_sparse: sync");
     if (c[2]) { gsr_set_error("tsdf_sparse: capacity exhausted (%u units) while merging", s->cap_blocks); return 1; }
+    if (c[3]) {      // cleared like frame_errors does: the volume stays usable
+        (void)gsr_memset_async((int32_t*)s->counters + 3, 0, sizeof(int32_t), st);
+        gsr_set_error("tsdf_sparse: a unit to merge lies outside the addressable volume (|unit coordinate| >= 2^20, i.e. %g scene units from the origin)",
+                      (double)(1 << 20) * s->voxel_length * TS_RES); return 1;
+    }
     return 0;
 }
 extern "C" int gsr_tsdf_sparse_merge(const gsr_tsdf_sparse* s, int32_t n_units, const int32_t* coords, const float* tsdf, const float* weight,

@@ -82,7 +82,9 @@ static inline int check_vol(const gsr_tsdf_sparse* s)
     if (!s || !s->keys || !s->slot || !s->coord || !s->stamp || !s->list || !s->counters || !s->mask) {
         gsr_set_error("tsdf_sparse: null volume buffers"); return 1;
     }
-    if (s->n_chunks < 1 || s->n_chunks > GSR_TSDF_MAX_CHUNKS || s->chunk0_log2 > 27 || s->cap_blocks != (1u << (s->chunk0_log2 + s->n_chunks - 1))) {
+    // (the shift count is checked first: chunk0_log2 + n_chunks - 1 can reach 50, and a 32-bit shift by 32 or more is undefined -- on x86 it wraps)
+    if (s->n_chunks < 1 || s->n_chunks > GSR_TSDF_MAX_CHUNKS || s->chunk0_log2 > 27 || s->chunk0_log2 + s->n_chunks - 1 > 31 ||
+        s->cap_blocks != (1u << (s->chunk0_log2 + s->n_chunks - 1))) {
         gsr_set_error("tsdf_sparse: %u chunks of first size 2^%u do not make a pool of %u units (chunk c >= 1 holds 2^(chunk0_log2 + c - 1) units)", s->n_chunks, s->chunk0_log2,
                       s->cap_blocks); return 1;
     }

@@ -287,20 +287,25 @@ class ScalableTSDFVolume:
         if tex is None or tex.numel() != 4 * f["H"] * f["W"]:
             tex = self._tex = torch.empty((f["H"] * f["W"], 4), dtype=torch.float32, device=self.device)
         st = self._struct()
+        self._status[f["slot"]].zero_()          # a call refused before it enqueues anything leaves the words alone: they must not be an earlier frame's
         with torch.cuda.device(self.device):
             rc = lib().gsr_tsdf_sparse_integrate2(C.byref(st), f["W"], f["H"], ptr(f["d"]), ptr(f["c"]), f["quant"], *f["intr"], f["Ea"], f["Pa"], f["dt"],
                                                   self.stride, self.frame, ptr(tex), C.c_void_p(self._status[f["slot"]].data_ptr()),
                                                   0 if sync else self.TSDF_NO_SYNC, stream_ptr(self.device))
         f["rc"] = rc
+        f["err"] = last_error() if rc != 0 else ""      # the library's error text is one global string: by the time a deferred frame is looked at it may be another call's
 
     def _frame_rc(self, f):
+        """-> (rc, error text, pool exhausted) of a frame whose status words are on the host.  Whether the pool ran out is read from the frame's own status
+        word, never from the error text."""
         import ctypes as C
-        rc = f["rc"]
+        rc, msg = f["rc"], f["err"]
         if rc == 0 and "event" in f:
             st = self._struct()
             with torch.cuda.device(self.device):
                 rc = lib().gsr_tsdf_sparse_status(C.byref(st), C.c_void_p(self._status[f["slot"]].data_ptr()), stream_ptr(self.device))
-        return rc
+            msg = last_error() if rc != 0 else ""
+        return rc, msg, rc != 0 and int(self._status[f["slot"], 2]) != 0
 
     def _resolve(self, frames):
         """Looks at the outcome of enqueued frames (oldest first) whose status words are on the host.  "Capacity exhausted": nothing of that frame nor of the
@@ -313,13 +318,12 @@ class ScalableTSDFVolume:
             if rerun:
                 f.pop("event", None)
                 self._enqueue(f, sync=True)
-            rc = self._frame_rc(f)
-            if rc != 0 and self.auto_grow and "capacity exhausted" in last_error() and self.cap < (1 << 27):
+            rc, msg, exhausted = self._frame_rc(f)
+            if exhausted and self.auto_grow and self.cap < (1 << 27):
                 self._grow()
                 rerun = True
                 continue
             if rc != 0:
-                msg = last_error()
                 self._after_failure()
                 raise RuntimeError(f"tsdf_sparse_integrate: {msg}")
             self.last_touched = int(self._status[f["slot"], 1]); self._allocated = int(self._status[f["slot"], 0])
@@ -329,7 +333,7 @@ class ScalableTSDFVolume:
         """Resolves the frames at the head of the queue whose event has already fired (no waiting)."""
         while self._queue and self._queue[0]["event"].query():
             f = self._queue[0]
-            if self._frame_rc(f) != 0:
+            if self._frame_rc(f)[0] != 0:
                 return self.finish()
             self.last_touched = int(self._status[f["slot"], 1]); self._allocated = int(self._status[f["slot"], 0])
             self._queue.pop(0)
@@ -464,11 +468,11 @@ class ScalableTSDFVolume:
             st = self._struct()
             with torch.cuda.device(self.device):
                 rc = call(st)
-            if rc != 0 and self.auto_grow and "capacity exhausted" in last_error() and self.cap < (1 << 27):
+            msg = last_error() if rc != 0 else ""
+            if rc != 0 and self.auto_grow and int(self.counters[2].item()) != 0 and self.cap < (1 << 27):      # the volume's own overflow word, not the text
                 self._grow()
                 continue
             if rc != 0:
-                msg = last_error()
                 self._after_failure()
                 raise RuntimeError(f"{what}: {msg}")
             self._allocated = min(int(self.counters[0].item()), self.cap)

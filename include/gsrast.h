@@ -252,7 +252,8 @@ int gsr_tsdf_sparse_status(const gsr_tsdf_sparse* vol, const int32_t* status_hos
 int gsr_tsdf_sparse_rehash(const gsr_tsdf_sparse* vol, int32_t n_units, void* stream);
 /* vol <- weighted merge with n_units units given as plain arrays in LOGICAL voxel order (coords [n,3] int32, tsdf/weight [n,16,16,16] x-major,
  * color [n,16,16,16,3]; weight 0 = no data): the fusion step of extract_mesh_split.py when every GPU integrated its own tile's frames (running averages are
- * associative in (sum w*tsdf, sum w)); the lists other ranks send. */
+ * associative in (sum w*tsdf, sum w)); the lists other ranks send.  A coordinate outside [-2^20 + 1, 2^20 - 2] has no key of its own: the call is refused
+ * ("outside the addressable volume", like a frame with such a sample) before any voxel is merged. */
 int gsr_tsdf_sparse_merge(const gsr_tsdf_sparse* vol, int32_t n_units, const int32_t* coords, const float* tsdf, const float* weight,
                           const float* color, void* stream);
 /* ABI 8.  vol <- weighted merge with units [0, n_units) of another volume on the same device, read where they lie (storage order, written-group words):

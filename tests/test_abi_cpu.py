@@ -174,3 +174,22 @@ def test_multiview_loss_argument_errors_without_a_device():
     good.patch = 3
     assert L.gsr_loss_plane_mv_ncc(C.byref(good), 4, None, a, a, a, a, a, None, None, a, a, a, a, big, None) != 0 and "null pointer" in gsrast.last_error()
     assert L.gsr_loss_plane_mv_scratch_bytes(1920, 1080, 102400) >= 8 * max(60 * 135, 6400)
+
+
+def test_sparse_tsdf_rejects_a_chunk_table_whose_capacity_shift_overflows():
+    """check_vol (gsr_tsdf_view.h) compared cap_blocks with 1u << (chunk0_log2 + n_chunks - 1); both fields passed their own range checks with the sum
+    at 32, where the 32-bit shift is undefined and wraps to 1u << 0 on x86: a one-unit pool with six chunks went through, and ts_unit would have indexed
+    chunks that do not exist.  No device is needed: the volume is refused before anything is launched."""
+    import ctypes as C
+    import gsrast
+    L = gsrast.lib()
+    buf = (C.c_float * 64)()
+    a = C.addressof(buf)
+    chunks = (C.c_void_p * gsrast.TsdfSparse.MAX_CHUNKS)(*[a] * gsrast.TsdfSparse.MAX_CHUNKS)
+    bad = gsrast.TsdfSparse(a, a, a, a, a, a, a, chunks, 27, 6, 4, 1, 0.02, 0.1)
+    assert L.gsr_tsdf_sparse_rehash(C.byref(bad), 0, None) != 0 and "do not make a pool" in gsrast.last_error()
+    assert L.gsr_tsdf_sparse_materialize(C.byref(bad), 0, None) != 0
+    good = gsrast.TsdfSparse(a, a, a, a, a, a, a, chunks, 4, 1, 5, 16, 0.02, 0.1)      # the same call on a well-formed volume: nothing to do
+    assert L.gsr_tsdf_sparse_rehash(C.byref(good), 0, None) == 0
+    top = gsrast.TsdfSparse(a, a, a, a, a, a, a, chunks, 27, 1, 28, 1 << 27, 0.02, 0.1)      # the largest first chunk is still admitted
+    assert L.gsr_tsdf_sparse_rehash(C.byref(top), 0, None) == 0
