@@ -79,7 +79,8 @@ EXPORTS = ["gsr_geom_bytes", "gsr_img_bytes", "gsr_binning_bytes", "gsr_backward
            "gsr_unbounded_lattice_points", "gsr_unbounded_lattice_tsdf", "gsr_unbounded_mc_scratch_bytes", "gsr_unbounded_mc_count", "gsr_unbounded_mc_emit",
            "gsr_unbounded_finish", "gsr_unbounded_texture",
            "gsr_cam_dist_quantiles_scratch_bytes", "gsr_cam_dist_quantiles", "gsr_select_lerp_scratch_bytes", "gsr_select_lerp",
-           "gsr_voxel_unique_scratch_bytes", "gsr_voxel_unique_count", "gsr_voxel_unique_emit"]
+           "gsr_voxel_unique_scratch_bytes", "gsr_voxel_unique_count", "gsr_voxel_unique_emit",
+           "gsr_view_select_scratch_bytes", "gsr_view_select"]
 PROF_LABELS = ["preprocess", "depth_order", "binning", "blend_fwd", "bwd_memset", "blend_bwd", "preprocess_bwd", "_"]
 
 _lib = None
@@ -173,6 +174,10 @@ def lib():
     L.gsr_voxel_unique_count.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, _vp, sz, _vp, _vp]
     L.gsr_voxel_unique_emit.restype = C.c_int
     L.gsr_voxel_unique_emit.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, _vp, sz, C.POINTER(C.c_uint32), _vp, _vp, _vp]
+    L.gsr_view_select_scratch_bytes.restype = sz; L.gsr_view_select_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.gsr_view_select.restype = C.c_int
+    L.gsr_view_select.argtypes = [_vp, C.c_int32, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _vp,
+                                  _vp, sz, _vp, _vp]
     L.gsr_adam_step_multi.restype = C.c_int
     L.gsr_adam_step_multi.argtypes = [C.c_int32, _vp, _vp]
     L.gsr_adam_step_multi_dev.restype = C.c_int

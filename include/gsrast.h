@@ -712,6 +712,33 @@ int gsr_voxel_unique_emit(const void* points, int64_t N, int32_t L, const double
                           size_t scratch_bytes, const uint32_t* record /*host [1 + L]*/, float* positions /*[sum,3]*/, int32_t* level /*[sum]*/,
                           void* stream);
 
+/* ---- neighbour views (PGSR's view_selection / calc_score, gssr/utils/mvsnet_utils.py:306-343; additions, no ABI bump).
+ * For C <= GSR_VIEWS_MAX_IMAGES images (an LDS row of C doubles per workgroup), M < 2^31 observations and Np < 2^31 points, everything in float64:
+ *   S[i,j] = S[j,i] = sum over the entries pid of image i's observations (i < j; in their multiplicity in image i), pid != -1 and observed by j, of
+ *       exp(-(theta - theta0)^2 / (2 s^2)),  theta = (180 / pi) acos(dot(ci - p, cj - p) / |ci - p| / |cj - p|),  s = theta <= theta0 ? sigma1 : sigma2
+ *   and S[i,i] = 0; near_ids / near_scores [C,k]: per image the k <= C best columns of its row, by descending score, among EQUAL scores the higher
+ *   index first (a stable ascending sort, reversed); the image's own index competes with its 0.  scores [C,C] is written where it is not NULL.
+ * obs_ids [M] are the images' point ids one image after the other, image a in [obs_offsets[a], obs_offsets[a + 1]); point_ids [Np] ascends strictly
+ * and point_xyz [Np,3] goes with it.  id_bits = 32 promises that no id other than -1 has a bit above 2^32 set (the sort then skips the high word;
+ * a broken promise sets GSR_VIEWS_ERR_ID_RANGE), 64 promises nothing.  The sums run over the shared points in ascending id: the order is a function
+ * of the input alone, two calls give the same bits and S is symmetric bit for bit; no floating-point atomics.
+ * *status_dev is cleared by the call and carries GSR_VIEWS_ERR_* bits afterwards (the outputs then mean nothing); the host wrapper reads it and raises:
+ *   NONFINITE  a centre or a term of a score is NaN or infinite (the reference leaves a NaN score in place)
+ *   ABSENT     an id that two or more distinct images observe has no row in point_ids (the reference's KeyError; seen by one image it is no error)
+ *   TABLE      point_ids does not ascend strictly          OFFSETS  obs_offsets does not ascend from 0 to M
+ *   ID_RANGE   id_bits = 32, but an id other than -1 is negative or 2^32 or more */
+#define GSR_VIEWS_MAX_IMAGES 16384
+#define GSR_VIEWS_ERR_NONFINITE 1u
+#define GSR_VIEWS_ERR_ABSENT 2u
+#define GSR_VIEWS_ERR_TABLE 4u
+#define GSR_VIEWS_ERR_OFFSETS 8u
+#define GSR_VIEWS_ERR_ID_RANGE 16u
+size_t gsr_view_select_scratch_bytes(int64_t M, int32_t C);
+int gsr_view_select(const double* centres /*[C,3]*/, int32_t C, const int64_t* obs_offsets /*[C + 1]*/, const int64_t* obs_ids /*[M]*/, int64_t M,
+                    const int64_t* point_ids /*[Np]*/, const double* point_xyz /*[Np,3]*/, int64_t Np, double theta0, double sigma1, double sigma2,
+                    int32_t k, int32_t id_bits, int32_t* near_ids /*[C,k]*/, double* near_scores /*[C,k]*/, double* scores /*[C,C] or NULL*/,
+                    void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[1]*/, void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
