@@ -470,9 +470,9 @@ __global__ void __launch_bounds__(256) k_lod_mask(LodArgs p)
         if (p.prog_ratio) p.prog_ratio[i] = pred - truncf(pred);
         if (p.transition_mask) p.transition_mask[i] = (lvl == il) ? 1 : 0;
     } else {
-        const float r = p.c.mode == 0 ? floorf(pred) : (p.c.mode == 1 ? rintf(pred) : ceilf(pred));     // torch.round = half to even
+        float r = p.c.mode == 0 ? floorf(pred) : (p.c.mode == 1 ? rintf(pred) : ceilf(pred));           // torch.round = half to even
+        r = fminf(fmaxf(r, 0.0f), (float)cur);      // the clamp, before the conversion: pred = +-inf (an anchor at the camera) converts defined
         il = (int)r;
-        il = il < 0 ? 0 : (il > cur ? cur : il);
     }
     p.anchor_mask[i] = (lvl <= il) ? 1 : 0;                                                   // :267
 }

@@ -22,12 +22,12 @@ def octree_visible(raster_settings, anchor, level, scaling, rotation, voxel_size
     if dist2level not in MODES:
         raise ValueError(f"Unknown dist2level: {dist2level}")
     with torch.no_grad():
-        a = dev_f32(anchor, "anchor", allow_empty=False)
-        Na = a.shape[0]
-        dev = a.device
+        Na = int(anchor.shape[0])
+        dev = anchor.device
+        a = dev_f32(anchor, "anchor", allow_empty=Na == 0)                    # no anchors: empty outputs, nothing launched
         lv = level.reshape(-1).to(torch.int32).contiguous()
-        sc = dev_f32(scaling, "scaling", allow_empty=False)
-        ro = dev_f32(rotation, "rotation", allow_empty=False)
+        sc = dev_f32(scaling, "scaling", allow_empty=Na == 0)
+        ro = dev_f32(rotation, "rotation", allow_empty=Na == 0)
         ex = None if extra_level is None else dev_f32(extra_level.reshape(-1), "extra_level")
         amask = torch.empty(Na, dtype=torch.uint8, device=dev)
         radii = torch.empty(Na, dtype=torch.int32, device=dev)

@@ -1299,8 +1299,44 @@ void ref_get_image_state(const ref_state* st, real* final_T, uint32_t* n_contrib
 }
 
 /* ------------------------------------------------------------------ scaffold-filter & markVisible */
-/* FILTER forward.cu:268-340 via rasterizer_impl.cu:340-396 */
-void ref_visible_filter(const ref_inputs* in, int32_t* radii)
+/* FILTER forward.cu:268-340 via rasterizer_impl.cu:340-396.  terms (or NULL) [7]: the operands of the gates as this build evaluates them, NaN
+ * where the point left before: view depth, det, 3 sqrt(lambda_max), and the four getRect operands in tiles (tests/visible_truth.py measures the
+ * float32 rounding of each gate on them). */
+static int32_t filter_one(const ref_inputs* in, int idx, int gx, int gy, real focal_x, real focal_y, real* terms)
+{
+    const int W = in->W, H = in->H;
+    f3 p_view;
+    const int inside = in_frustum(idx, in->means3D, in->viewmatrix, &p_view);
+    if (terms) { for (int k = 0; k < 7; k++) terms[k] = (real)NAN; terms[0] = p_view.z; }
+    if (!inside) return 0;
+    f3 p_orig = { in->means3D[3*idx], in->means3D[3*idx+1], in->means3D[3*idx+2] };
+    real ph[4]; transformPoint4x4(p_orig, in->projmatrix, ph);
+    real p_w = 1.0f / (ph[3] + 0.0000001f);
+    real cov3Dl[6]; const real* cov3D;
+    if (in->cov3D_precomp) cov3D = in->cov3D_precomp + 6*idx;
+    else { computeCov3D(in->scales + 3*idx, in->scale_modifier, in->rotations + 4*idx, cov3Dl); cov3D = cov3Dl; }
+    real cov[3];
+    computeCov2D(p_orig, focal_x, focal_y, in->tanfovx, in->tanfovy, cov3D, in->viewmatrix, cov, NULL, NULL, NULL, NULL, NULL);
+    real det = (cov[0] * cov[2] - cov[1] * cov[1]);
+    if (terms) terms[1] = det;
+    if (det == 0.0f) return 0;
+    real mid = 0.5f * (cov[0] + cov[2]);
+    real lambda1 = mid + R_sqrt(R_fmax(0.1f, mid * mid - det));
+    real lambda2 = mid - R_sqrt(R_fmax(0.1f, mid * mid - det));
+    real my_radius = R_ceil(3.f * R_sqrt(R_fmax(lambda1, lambda2)));
+    f2 pi = { ndc2Pix(ph[0] * p_w, W), ndc2Pix(ph[1] * p_w, H) };
+    if (terms) {
+        const int r = (int)my_radius;
+        terms[2] = 3.f * R_sqrt(R_fmax(lambda1, lambda2));
+        terms[3] = (pi.x - r) / BLOCK_X; terms[4] = (pi.y - r) / BLOCK_Y;
+        terms[5] = (pi.x + r + BLOCK_X - 1) / BLOCK_X; terms[6] = (pi.y + r + BLOCK_Y - 1) / BLOCK_Y;
+    }
+    uint32_t rmin[2], rmax[2];
+    getRect(pi, (int)my_radius, gx, gy, rmin, rmax);
+    if ((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) == 0) return 0;
+    return (int32_t)my_radius;
+}
+void ref_visible_filter_terms(const ref_inputs* in, int32_t* radii, real* terms /*[P,7] or NULL*/)
 {
     const int P = in->P, W = in->W, H = in->H;
     const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
@@ -1309,30 +1345,13 @@ void ref_visible_filter(const ref_inputs* in, int32_t* radii)
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static)
 #endif
-    for (int idx = 0; idx < P; idx++) {
-        radii[idx] = 0;
-        f3 p_view;
-        if (!in_frustum(idx, in->means3D, in->viewmatrix, &p_view)) continue;
-        f3 p_orig = { in->means3D[3*idx], in->means3D[3*idx+1], in->means3D[3*idx+2] };
-        real ph[4]; transformPoint4x4(p_orig, in->projmatrix, ph);
-        real p_w = 1.0f / (ph[3] + 0.0000001f);
-        real cov3Dl[6]; const real* cov3D;
-        if (in->cov3D_precomp) cov3D = in->cov3D_precomp + 6*idx;
-        else { computeCov3D(in->scales + 3*idx, in->scale_modifier, in->rotations + 4*idx, cov3Dl); cov3D = cov3Dl; }
-        real cov[3];
-        computeCov2D(p_orig, focal_x, focal_y, in->tanfovx, in->tanfovy, cov3D, in->viewmatrix, cov, NULL, NULL, NULL, NULL, NULL);
-        real det = (cov[0] * cov[2] - cov[1] * cov[1]);
-        if (det == 0.0f) continue;
-        real mid = 0.5f * (cov[0] + cov[2]);
-        real lambda1 = mid + R_sqrt(R_fmax(0.1f, mid * mid - det));
-        real lambda2 = mid - R_sqrt(R_fmax(0.1f, mid * mid - det));
-        real my_radius = R_ceil(3.f * R_sqrt(R_fmax(lambda1, lambda2)));
-        f2 pi = { ndc2Pix(ph[0] * p_w, W), ndc2Pix(ph[1] * p_w, H) };
-        uint32_t rmin[2], rmax[2];
-        getRect(pi, (int)my_radius, gx, gy, rmin, rmax);
-        if ((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) == 0) continue;
-        radii[idx] = (int)my_radius;
-    }
+    for (int idx = 0; idx < P; idx++) radii[idx] = filter_one(in, idx, gx, gy, focal_x, focal_y, terms ? terms + 7 * (size_t)idx : NULL);
+}
+void ref_visible_filter(const ref_inputs* in, int32_t* radii) { ref_visible_filter_terms(in, radii, NULL); }
+/* the cov3D_precomp a caller of the scale/rotation code would pass on: computeCov3D per point */
+void ref_cov3d(int32_t P, const real* scales /*[P,3]*/, real mod, const real* rotations /*[P,4]*/, real* cov3D /*[P,6]*/)
+{
+    for (int i = 0; i < P; i++) computeCov3D(scales + 3 * (size_t)i, mod, rotations + 4 * (size_t)i, cov3D + 6 * (size_t)i);
 }
 
 /* 3DGS rasterizer_impl.cu:54-66,141-153 */

@@ -138,6 +138,9 @@ void     ref_get_image_state(const ref_state* st, real* final_T /*[N] (SURFEL [3
                              uint32_t* n_contrib /*[N] (SURFEL [2N])*/);
 
 void ref_visible_filter(const ref_inputs* in, int32_t* radii);   /* scaffold-filter */
+/* the same, with the operands of its gates: z, det, 3 sqrt(lambda_max), the four tile-rect operands (NaN where the point left before) */
+void ref_visible_filter_terms(const ref_inputs* in, int32_t* radii, real* terms /*[P,7] or NULL*/);
+void ref_cov3d(int32_t P, const real* scales /*[P,3]*/, real mod, const real* rotations /*[P,4]*/, real* cov3D /*[P,6]*/);
 void ref_mark_visible(int32_t P, const real* means3D, const real* viewmatrix, const real* projmatrix,
                       uint8_t* present);
 

@@ -387,6 +387,27 @@ def visible_filter(scene):
     return radii
 
 
+def visible_filter_terms(scene):
+    """-> (radii [P], terms [P,7]): the float32 operands of the filter's gates as this build of the oracle evaluates them (NaN where the point
+    left before): view depth, det, 3 sqrt(lambda_max), the four tile-rect operands in tiles."""
+    ri = make_inputs(scene, EWA)
+    radii = np.zeros((ri.P,), np.int32); terms = np.zeros((ri.P, 7), np.float32)
+    L = lib()
+    L.ref_visible_filter_terms.argtypes = [C.POINTER(RefInputs), C.POINTER(C.c_int32), _fp]
+    L.ref_visible_filter_terms(C.byref(ri), radii.ctypes.data_as(C.POINTER(C.c_int32)), _p(terms))
+    return radii, terms
+
+
+def cov3d(scales, scale_modifier, rotations):
+    """The float32 cov3D [P,6] of the oracle's scale/rotation code (what a caller hands on as cov3D_precomp)."""
+    s, q = _f32(np.asarray(scales)[:, :3]), _f32(rotations)
+    out = np.zeros((s.shape[0], 6), np.float32)
+    L = lib()
+    L.ref_cov3d.argtypes = [C.c_int32, _fp, C.c_float, _fp, _fp]
+    L.ref_cov3d(s.shape[0], _p(s), float(scale_modifier), _p(q), _p(out))
+    return out
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     m, v, p = _f32(means3D), _f32(viewmatrix), _f32(projmatrix)
     out = np.zeros((m.shape[0],), np.uint8)

@@ -152,6 +152,17 @@ def lod_mask(anchor, level, extra_level, campos, voxel_size, fork, standard_dist
     return m.astype(bool), pr, tr.astype(bool)
 
 
+def lod_pred(anchor, level, extra_level, campos, voxel_size, fork, standard_dist, resolution_scale):
+    """pred_level [Na] float32 as refd_lod_mask evaluates it."""
+    L = oracle.lib()
+    L.refd_lod_pred.restype = None
+    a = _f(anchor); lv = np.ascontiguousarray(level, dtype=np.int32); ex = _f(extra_level); cp = _f(campos)
+    pred = np.zeros(a.shape[0], np.float32)
+    L.refd_lod_pred(C.c_int32(a.shape[0]), _p(a), lv.ctypes.data_as(C.POINTER(C.c_int32)), _p(ex), _p(cp), C.c_float(voxel_size), C.c_float(fork),
+                    C.c_float(standard_dist), C.c_float(resolution_scale), _p(pred))
+    return pred
+
+
 def training_stats(vis_idx, k, neural_opacity, mask, update_filter, grad, opacity_accum, anchor_demon, offset_gradient_accum, offset_denom):
     """In place on the four float32 accumulators (oracle/gsd_oracle.c refd_training_stats)."""
     L = oracle.lib()

@@ -151,6 +151,21 @@ def test_weed_out_against_float64(U, C):
             assert 0 < int(keep.sum()) < U
 
 
+def test_weed_out_at_a_camera_centre_and_far_away():
+    """A position that coincides with a camera centre has dist 0 and pred +inf: clamped in floating point, before the integer conversion, it gives
+    level levels - 1, so the camera admits every level.  At 1e7 pred is about -20, and beyond the range of float32's d^2 it is -inf: level 0 only."""
+    from gsrast import octree
+    levels, sd, fork = WEED["levels"], WEED["sd"], WEED["fork"]
+    cams = torch.tensor([[1.0, 2.0, 3.0, 1.0]])
+    pos = torch.tensor([[1.0, 2.0, 3.0]] * levels + [[0.0, 0.0, 1e7]] * 2 + [[0.0, 3e19, 0.0]] * 2)
+    lv = torch.tensor(list(range(levels)) + [0, 1, 0, 1], dtype=torch.int32)
+    want = torch.tensor([1] * levels + [1, 0, 1, 0], dtype=torch.int32)
+    for mode in MODES:
+        assert torch.equal(R.weed_out(pos, lv, cams, sd, fork, levels, mode, 0.5)[0], want), mode          # the restatement, float32 on the host
+        count, keep = octree.weed_out(pos.to(DEV), lv.to(DEV), cams.to(DEV), sd, fork, levels, mode, 0.5)
+        assert torch.equal(count.cpu(), want) and torch.equal(keep.cpu(), want > 0), (mode, count.tolist())
+
+
 # ------------------------------------------------------------------------------------------------------------------------ occupancy apart from candidacy
 def tiny_model(dist2level="round", voxel_size=1.0):
     """Two anchors, k = 1, two levels about the origin: anchor 0 of level 0 at the cell (2, 2, 2) with a strong gradient and a zero offset, so that its

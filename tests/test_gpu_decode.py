@@ -8,6 +8,7 @@ import decode_cases
 import decode_truth
 import oracle_decode
 import ref_decode_torch
+import visible_truth
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -133,13 +134,18 @@ def test_octree_visible_matches_oracle(mode):
                                 dist2level=mode, extra_level=torch.tensor(extra, device=DEV))
     hm = out["anchor_mask"].cpu().numpy()
     flips = hm != m
-    assert flips.mean() < 2e-4                                                # log2f / rounding boundary cases only
+    # a flip is allowed only where the float64 truth puts pred within its measured float32 bound of a rounding boundary (tests/visible_truth.py)
+    truth = visible_truth.lod(sc["means3D"], level, extra, sc["campos"], vs, fork, sd, 1.0, levels, mode)
+    frag = truth["margin"] <= visible_truth.BOUND["pred"]
+    print(f"{mode}: fragile {int(frag.sum())} of {Na}, device flips against the oracle {int(flips.sum())}")
+    assert frag.mean() < 2e-4 and not (flips & ~frag).any()
+    assert np.array_equal(hm[~frag], truth["anchor_mask"][~frag])
     ok = ~flips
     assert np.array_equal(out["radii"].cpu().numpy()[ok], rad[ok])
     assert np.array_equal(out["visible_mask"].cpu().numpy()[ok], (rad > 0)[ok]) and out["visible_mask"].any()
     if mode == "progressive":
-        assert np.abs(out["prog_ratio"].cpu().numpy().ravel() - pr)[ok].max() < 1e-3 or True
-        assert (out["transition_mask"].cpu().numpy() != tr).mean() < 2e-4
+        assert np.abs(out["prog_ratio"].cpu().numpy().ravel() - pr)[~frag].max() < 1e-3
+        assert not ((out["transition_mask"].cpu().numpy() != tr) & ~frag).any()
 
 
 def test_padded_visible_list_gives_identical_gaussians_without_the_count_sync():
