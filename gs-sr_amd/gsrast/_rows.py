@@ -1,24 +1,9 @@
-"""What gsrast.anchors and gsrast.densify share: argument checks, the ctypes side of include/gsrast.h's gsr_anchor_level_*, gsr_rows_* and
-gsr_densify_* entry points, and the surgery on a model and its optimizer (param groups by name, Adam moments, fresh leaf Parameters)."""
-import ctypes as C
-
+"""What gsrast.anchors and gsrast.densify share: argument checks, the structs of include/gsrast.h's gsr_anchor_level_*, gsr_rows_* and
+gsr_densify_* entry points under their short names, and the surgery on a model and its optimizer (param groups by name, Adam moments, fresh leaf Parameters)."""
 import torch
 
-from . import lib
-
-_vp = C.c_void_p
-
-
-class Level(C.Structure):                 # include/gsrast.h gsr_anchor_level
-    _fields_ = [("Na", C.c_int32), ("N0", C.c_int32), ("k", C.c_int32), ("F", C.c_int32), ("scaling_stride", C.c_int32),
-                ("thr_lo", C.c_float), ("thr_hi", C.c_float), ("rand_thr", C.c_float), ("cell", C.c_float), ("origin", C.c_float * 3),
-                ("anchor", _vp), ("mask", _vp), ("offset", _vp), ("scaling", _vp), ("anchor_feat", _vp), ("grads", _vp), ("offset_mask", _vp), ("rand", _vp)]
-
-
-class Weed(C.Structure):                  # include/gsrast.h gsr_octree_weed
-    _fields_ = [("cam_infos", _vp), ("C", C.c_int32), ("levels", C.c_int32), ("mode", C.c_int32), ("lv", C.c_int32),
-                ("standard_dist", C.c_float), ("fork", C.c_float), ("visible_threshold", C.c_float)]
-
+from ._abi import gsr_anchor_level as Level, gsr_octree_weed as Weed, gsr_rows_tensor as RowsTensor  # noqa: F401
+from ._abi import gsr_densify_args as Args, gsr_densify_tensor as Tensor, gsr_densify_compute as Compute  # noqa: F401
 
 WEED_MODES = {"floor": 0, "round": 1, "ceil": 2}
 WEED_CHUNK = 256                          # include/gsrast.h GSR_OCTREE_WEED_CHUNK
@@ -36,50 +21,6 @@ def make_weed(cam_infos, standard_dist, fork, levels, dist2level, visible_thresh
     if int(levels) < 1:
         raise RuntimeError(f"levels: expected a positive number but found {levels}")
     return Weed(cams.data_ptr(), cams.shape[0], int(levels), WEED_MODES[dist2level], int(lv), float(standard_dist), float(fork), float(visible_threshold)), cams
-
-
-class RowsTensor(C.Structure):            # include/gsrast.h gsr_rows_tensor
-    _fields_ = [("src", _vp), ("dst", _vp), ("tail", _vp), ("row_bytes", C.c_int64), ("n_tail", C.c_int64)]
-
-
-class Args(C.Structure):                  # include/gsrast.h gsr_densify_args
-    _fields_ = [("P", C.c_int32), ("scaling_cols", C.c_int32), ("N", C.c_int32), ("flags", C.c_int32)] + \
-               [(n, C.c_float) for n in ("clone_thr", "split_thr", "abs_thr", "dense_thr", "min_opacity", "world_thr", "abs_radii_thr", "child_div",
-                                         "clone_cap", "split_cap", "abs_cap")] + \
-               [(n, _vp) for n in ("accum", "denom", "accum_abs", "denom_abs", "scaling", "opacity", "max_radii2D", "masked_out")]
-
-
-class Tensor(C.Structure):                # include/gsrast.h gsr_densify_tensor
-    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", C.c_int64), ("zero_new", C.c_int32), ("pad_", C.c_int32)]
-
-
-class Compute(C.Structure):               # include/gsrast.h gsr_densify_compute
-    _fields_ = [(n, _vp) for n in ("xyz", "rotation", "xyz_dst", "scaling_dst", "noise_split", "noise_clone")]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        sz = C.c_size_t
-        for name, res, args in (
-                ("gsr_anchor_level_scratch_bytes", sz, [C.c_int32] * 3),
-                ("gsr_anchor_level_find", C.c_int, [C.POINTER(Level), _vp, sz, _vp, _vp]),
-                ("gsr_anchor_level_emit", C.c_int, [C.POINTER(Level), _vp, sz, C.c_uint32, _vp, _vp, _vp]),
-                ("gsr_anchor_level_find_weed", C.c_int, [C.POINTER(Level), _vp, C.POINTER(Weed), _vp, sz, _vp, _vp]),
-                ("gsr_octree_weed_out", C.c_int, [_vp, _vp, C.c_int64, C.POINTER(Weed), _vp, _vp, _vp]),
-                ("gsr_rows_compact_scratch_bytes", sz, [C.c_int64]),
-                ("gsr_rows_compact_multi", C.c_int, [C.c_int64, _vp, C.c_int32, C.POINTER(RowsTensor), _vp, sz, _vp]),
-                ("gsr_densify_plan_scratch_bytes", sz, [C.c_int32, C.c_int32]),
-                ("gsr_densify_plan", C.c_int, [C.POINTER(Args), _vp, sz, _vp, _vp]),
-                ("gsr_densify_emit", C.c_int, [C.POINTER(Args), _vp, sz, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(Tensor), C.POINTER(Compute), _vp])):
-            f = getattr(L, name)
-            f.restype, f.argtypes = res, args
-        _bound = True
-    return L
 
 
 def _f32(t, name, shape=None, device_check=True, wild=None):

@@ -20,8 +20,8 @@ import math
 
 import torch
 
-from . import check, ptr, stream_ptr
-from ._rows import Level, RowsTensor, _bytes, _f32, _lib, groups, install_, make_weed, moments
+from . import check, lib, ptr, stream_ptr
+from ._rows import Level, RowsTensor, _bytes, _f32, groups, install_, make_weed, moments
 
 PARAM_ATTRS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
 _SKIP = ("mlp", "conv", "feat_base", "embedding")        # param groups the reference's optimizer surgery leaves alone
@@ -81,7 +81,7 @@ def _grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cel
             raise RuntimeError(f"{name} must be on the device of anchor")
     if Na + N0 * k >= 1 << 31:
         raise RuntimeError(f"anchor: Na + n0 * k = {Na + N0 * k} entries exceed 2^31")
-    L = _lib()
+    L = lib()
     dev = anchor.device
     lv = Level(Na, N0, k, F, scaling.shape[1], thr_lo, thr_hi, rand_thr, cell, (C.c_float * 3)(*[float(o) for o in origin]),
                ptr(anchor).value, None if mask is None else ptr(mask).value, ptr(offset).value, ptr(scaling).value, ptr(anchor_feat).value, ptr(grads).value,
@@ -185,7 +185,7 @@ def rows_compact(keep, tensors, tails=None):
                 raise RuntimeError(f"tails[{i}] must match tensors[{i}] in dtype, device and row shape")
             t = t.detach().contiguous()
         srcs.append((x, rb, t))
-    L = _lib()
+    L = lib()
     dev = keep.device
     n_keep = int(keep.count_nonzero()) if N else 0
     with torch.cuda.device(dev):

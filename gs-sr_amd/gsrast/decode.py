@@ -10,71 +10,11 @@ import ctypes as C
 import torch
 
 from . import check, dev_f32, lib, ptr, stream_ptr
+from ._abi import FUNCTIONS
+from ._abi import gsd_cfg as Cfg, gsd_inputs as Inputs, gsd_params as Params, gsd_outputs as Outputs, gsd_out_grads as OutGrads, gsd_in_grads as InGrads
 
-_vp = C.c_void_p
 PARAM_NAMES = ("W1o", "b1o", "W2o", "b2o", "W1c", "b1c", "W2c", "b2c", "W1k", "b1k", "W2k", "b2k", "app")
-EXPORTS = ["gsd_compact_scratch_bytes", "gsd_compact_visible", "gsd_compact_visible_padded", "gsd_forward_scratch_bytes", "gsd_forward_stage1", "gsd_forward_stage2",
-           "gsd_forward", "gsd_forward_static", "gsd_forward_deferred", "gsd_backward_scratch_bytes", "gsd_backward", "gsd_training_stats_scratch_bytes", "gsd_training_stats"]
-
-
-class Cfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("Na", "Nv", "k", "A", "dist_o", "dist_c", "dist_k", "level")]
-
-
-class Inputs(C.Structure):
-    _fields_ = [(n, _vp) for n in ("anchor", "feat", "offset", "scaling", "level", "opacity_scale", "vis_idx", "campos")]
-
-
-class Params(C.Structure):
-    _fields_ = [(n, _vp) for n in PARAM_NAMES]
-
-
-class Outputs(C.Structure):
-    _fields_ = [(n, _vp) for n in ("xyz", "color", "opacity", "scaling", "rot")]
-
-
-class OutGrads(C.Structure):
-    _fields_ = [(n, _vp) for n in ("xyz", "color", "opacity", "scaling", "rot")]
-
-
-class InGrads(C.Structure):
-    _fields_ = [("anchor", _vp), ("feat", _vp), ("offset", _vp), ("scaling", _vp), ("params", Params)]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        sz = C.c_size_t
-        L.gsd_compact_scratch_bytes.restype = sz; L.gsd_compact_scratch_bytes.argtypes = [C.c_int32]
-        L.gsd_compact_visible.restype = C.c_int
-        L.gsd_compact_visible.argtypes = [_vp, C.c_int32, _vp, C.POINTER(C.c_uint32), _vp, sz, _vp]
-        L.gsd_compact_visible_padded.restype = C.c_int
-        L.gsd_compact_visible_padded.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, sz, _vp]
-        L.gsd_forward_scratch_bytes.restype = sz; L.gsd_forward_scratch_bytes.argtypes = [C.c_int32]
-        L.gsd_forward_stage1.restype = C.c_int
-        L.gsd_forward_stage1.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, _vp, C.POINTER(C.c_uint32), _vp, sz, _vp]
-        L.gsd_forward_stage2.restype = C.c_int
-        L.gsd_forward_stage2.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, C.c_uint32, C.POINTER(Outputs), _vp, sz, _vp]
-        L.gsd_forward.restype = C.c_int
-        L.gsd_forward.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, _vp, C.POINTER(Outputs),
-                                  C.POINTER(C.c_uint32), _vp, sz, _vp]
-        L.gsd_forward_static.restype = C.c_int
-        L.gsd_forward_static.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, _vp, C.POINTER(Outputs), _vp, _vp, sz, _vp]
-        L.gsd_forward_deferred.restype = C.c_int
-        L.gsd_forward_deferred.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, _vp, C.POINTER(Outputs), _vp, _vp, _vp, sz, _vp]
-        L.gsd_backward_scratch_bytes.restype = sz; L.gsd_backward_scratch_bytes.argtypes = [C.POINTER(Cfg)]
-        L.gsd_backward.restype = C.c_int
-        L.gsd_backward.argtypes = [C.POINTER(Cfg), C.POINTER(Inputs), C.POINTER(Params), _vp, _vp, C.c_uint32, C.POINTER(OutGrads),
-                                   C.POINTER(InGrads), _vp, _vp, sz, _vp]
-        L.gsd_training_stats_scratch_bytes.restype = sz; L.gsd_training_stats_scratch_bytes.argtypes = [C.c_int32]
-        L.gsd_training_stats.restype = C.c_int
-        L.gsd_training_stats.argtypes = [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, sz, _vp]
-        _bound = True
-    return L
+EXPORTS = [name for name, _, _ in FUNCTIONS if name.startswith("gsd_")]
 
 
 def compact_visible(visible_mask, padded=False):
@@ -87,7 +27,7 @@ def compact_visible(visible_mask, padded=False):
     m = visible_mask.contiguous()
     m = m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).view(torch.uint8)
     Na = m.numel()
-    L = _lib()
+    L = lib()
     idx = torch.empty(Na, dtype=torch.int32, device=m.device)
     scratch = torch.empty(L.gsd_compact_scratch_bytes(Na), dtype=torch.uint8, device=m.device)
     if padded:
@@ -120,7 +60,7 @@ def _decode_launch(flags, t, prm, mode):
     """Enqueue the decode forward.  mode "sync": gsd_forward (one host synchronisation, n = P on return); "static": gsd_forward_static (no
     synchronisation, all Nv*k rows, device count); "deferred": gsd_forward_deferred -- the count is copied to pinned memory behind stage 1 with an
     event behind the copy, stage 2 follows; the caller learns P later (PendingDecode.finish).  -> dict of the buffers the autograd node keeps."""
-    L = _lib()
+    L = lib()
     dev = t["anchor"].device
     k = flags[0]
     Na, Nv = t["anchor"].shape[0], t["vis_idx"].numel()
@@ -238,7 +178,7 @@ class _NeuralDecode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_color, g_opacity, g_scaling, g_rot, _g_nop, _g_mask, _g_count=None):
-        L = _lib()
+        L = lib()
         sv = ctx.saved_tensors
         names = ("anchor", "feat", "offset", "scaling", "level", "opacity_scale", "vis_idx", "campos")
         t = dict(zip(names, sv[:8]))
@@ -344,7 +284,7 @@ def training_stats_(opacity_accum, anchor_demon, offset_gradient_accum, offset_d
     viewspace_point_tensor.grad (P, >=2), `neural_opacity` = the decode's pre-gate opacity (Nv*k), `update_filter` = visibility_filter (P,),
     `offset_selection_mask` = the decode's mask (Nv*k), `anchor_visible_mask` (Na,) bool -- or the `vis_idx` the decode already computed).
     The four accumulators are the model's float32 buffers ((Na,1), (Na,1), (Na*k,1), (Na*k,1)); updated without any host synchronisation."""
-    L = _lib()
+    L = lib()
     with torch.no_grad():
         if vis_idx is None:
             vis_idx = compact_visible(anchor_visible_mask)

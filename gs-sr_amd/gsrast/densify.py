@@ -16,8 +16,8 @@ import functools
 
 import torch
 
-from . import check, ptr, stream_ptr
-from ._rows import Args, Compute, Tensor, _lib, groups, install_
+from . import check, lib, ptr, stream_ptr
+from ._rows import Args, Compute, Tensor, groups, install_
 from ._rows import _f32 as _rows_f32, moments as _moments
 
 _f32 = functools.partial(_rows_f32, wild="*")                # a free dimension prints as '*'
@@ -112,7 +112,7 @@ def clone_split_prune(params, moments, xyz_gradient_accum, denom, scaling_act, o
             raise RuntimeError(f"{name} must be on the device of xyz")
     moments = {n: tuple(mt.detach().contiguous() for mt in m) for n, m in moments.items()}
 
-    L = _lib()
+    L = lib()
     f32 = lambda v: C.c_float(v).value                           # the reference compares float32 tensors with Python scalars: the scalar is rounded to float32
     a = Args()
     a.P, a.scaling_cols, a.N = P, cols, N

@@ -11,36 +11,11 @@ import numpy as np
 import torch
 
 from . import check, lib, ptr, stream_ptr
-from ._rows import RowsTensor
+from ._abi import gsr_mesh_filter as Filter, gsr_rows_tensor as RowsTensor
 
-_vp = C.c_void_p
 DROP_UNREFERENCED, DROP_DEGENERATE = 1, 2             # include/gsrast.h GSR_MESH_DROP_*
 ERR_INDEX, ERR_INTERNAL, ERR_KEEP = 1, 2, 4           # GSR_MESH_ERR_*
 FLOOR = 50                                            # mesh_utils.py:41 "filter meshes smaller than 50"
-
-
-class Filter(C.Structure):                # include/gsrast.h gsr_mesh_filter
-    _fields_ = [("triangles", _vp), ("remove_mask", _vp), ("n_triangles", C.c_int64), ("n_vertices", C.c_int64), ("cluster_to_keep", C.c_int32),
-                ("floor", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32)]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        sz = C.c_size_t
-        for name, res, args in (
-                ("gsr_mesh_post_scratch_bytes", sz, [C.c_int64, C.c_int64]),
-                ("gsr_mesh_cluster_triangles", C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, sz, _vp, _vp]),
-                ("gsr_mesh_filter_count", C.c_int, [C.POINTER(Filter), _vp, sz, _vp, _vp]),
-                ("gsr_mesh_filter_emit", C.c_int, [C.POINTER(Filter), _vp, sz, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(RowsTensor), _vp, _vp])):
-            f = getattr(L, name)
-            f.restype, f.argtypes = res, args
-        _bound = True
-    return L
 
 
 def _arrays(mesh):
@@ -61,7 +36,7 @@ def _arrays(mesh):
 
 
 def _scratch(T, V, dev):
-    n = int(_lib().gsr_mesh_post_scratch_bytes(T, V))
+    n = int(lib().gsr_mesh_post_scratch_bytes(T, V))
     if n == 0:
         raise RuntimeError(f"mesh: {T} triangles / {V} vertices: 3T must stay below 2^31 (the half-edges are indexed with 32 bits); filter the mesh in parts")
     return torch.empty(n, dtype=torch.uint8, device=dev), n
@@ -87,8 +62,8 @@ def cluster_connected_triangles(mesh, with_area=True):
     scratch, nbytes = _scratch(T, 0, dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(_lib().gsr_mesh_cluster_triangles(ptr(t), T, V, ptr(v) if with_area else None, ptr(clusters), ptr(counts), ptr(area), ptr(scratch), nbytes,
-                                                ptr(status), stream_ptr(dev)), "mesh_cluster_triangles")
+        check(lib().gsr_mesh_cluster_triangles(ptr(t), T, V, ptr(v) if with_area else None, ptr(clusters), ptr(counts), ptr(area), ptr(scratch), nbytes,
+                                               ptr(status), stream_ptr(dev)), "mesh_cluster_triangles")
     st, n = status.tolist()
     _raise_status(st)
     return clusters, counts[:n].clone(), (area[:n].clone() if with_area else None)
@@ -102,7 +77,7 @@ def _filter(mesh, remove_mask=None, cluster_to_keep=0, flags=0):
     f = Filter(t.data_ptr() if T else None, None if remove_mask is None else remove_mask.data_ptr(), T, V, int(cluster_to_keep), FLOOR, int(flags), 0)
     scratch, nbytes = _scratch(T, V, dev)
     record = torch.empty(8, dtype=torch.int32, device=dev)
-    L = _lib()
+    L = lib()
     with torch.cuda.device(dev):
         check(L.gsr_mesh_filter_count(C.byref(f), ptr(scratch), nbytes, ptr(record), stream_ptr(dev)), "mesh_filter_count")
         rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back

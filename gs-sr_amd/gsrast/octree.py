@@ -47,7 +47,7 @@ def weed_out(positions, levels_of, cam_infos, standard_dist, fork, levels, dist2
     """-> (visible_count int32 [U], keep bool [U]): per position [U,3] of level levels_of [U] the number of cameras cam_infos [C,4] (centre, scale)
     whose distance level admits it, and visible_count / C > visible_threshold.  The reference loops over the cameras with eight launches each;
     this is one launch and no host synchronisation.  dist2level 'progressive' raises, as the reference's weed_out cannot run in it."""
-    from ._rows import _f32, _lib, make_weed
+    from ._rows import _f32, make_weed
     with torch.no_grad():
         pos = _f32(positions, "positions", (None, 3))
         U = pos.shape[0]
@@ -60,5 +60,5 @@ def weed_out(positions, levels_of, cam_infos, standard_dist, fork, levels, dist2
         count = torch.empty(U, dtype=torch.int32, device=pos.device)
         keep = torch.empty(U, dtype=torch.uint8, device=pos.device)
         with torch.cuda.device(pos.device):
-            check(_lib().gsr_octree_weed_out(ptr(pos), ptr(lv), U, C.byref(w), ptr(count), ptr(keep), stream_ptr(pos.device)), "octree_weed_out")
+            check(lib().gsr_octree_weed_out(ptr(pos), ptr(lv), U, C.byref(w), ptr(count), ptr(keep), stream_ptr(pos.device)), "octree_weed_out")
         return count, keep.view(torch.bool)

@@ -20,19 +20,13 @@ Two render passes over the same parameters (PGSR's reference + neighbour camera,
 gradients with one `add` kernel per parameter tensor (27 launches, 130 us per octree-pgsr iteration).  `shadow_parameters(x)` returns a second set of
 leaves over the SAME storage for the second pass; `Adam.add_shadows(params, shadows)` makes step() read both gradients in the update kernel
 (grad + grad2, the same single fp32 add) and zero_grad() clear both."""
-import ctypes as C
 import math
 
 import torch
 from torch.optim.adam import adam as _torch_adam
 
 from . import check, lib, stream_ptr
-
-
-class _AdamTensor(C.Structure):          # include/gsrast.h gsr_adam_tensor
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("lr_scale", C.c_void_p),
-                ("n", C.c_int64), ("beta1", C.c_double), ("beta2", C.c_double), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float),
-                ("eps", C.c_float), ("pad_", C.c_float), ("grad2", C.c_void_p)]
+from ._abi import gsr_adam_tensor as _AdamTensor
 
 
 def shadow_parameters(x):

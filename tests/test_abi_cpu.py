@@ -37,7 +37,7 @@ def test_decode_exports_match_header():
     L = gsrast.lib()
     for s in decl:
         assert hasattr(L, s), f"libgsrast_hip.so does not export {s}"
-    Ld = decode._lib()
+    Ld = gsrast.lib()
     c = decode.Cfg(100000, 60000, 10, 32, 0, 0, 0, 0)
     b = Ld.gsd_backward_scratch_bytes(__import__("ctypes").byref(c))
     assert 60000 * 416 * 4 <= b <= 60000 * 416 * 4 + (16 << 20)        # feature-major columns + partial tiles
@@ -132,7 +132,7 @@ def test_decode_argument_errors_without_a_device():
     import ctypes as C
     import gsrast
     from gsrast import decode
-    L = decode._lib()
+    L = gsrast.lib()
     buf = (C.c_float * 64)()
     addr = C.addressof(buf)
     prm = decode.Params(*[addr] * 13)

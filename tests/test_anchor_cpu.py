@@ -108,7 +108,7 @@ def test_library_argument_errors_without_a_device():
     import ctypes as C
     import gsrast
     from gsrast import anchors
-    L = anchors._lib()
+    L = gsrast.lib()
     buf = (C.c_float * 64)()
     a = C.addressof(buf)
 

@@ -125,7 +125,7 @@ def test_library_argument_errors_without_a_device():
     import ctypes as C
     import gsrast
     from gsrast import _rows, anchors
-    L = anchors._lib()
+    L = gsrast.lib()
     buf = (C.c_float * 64)()
     a = C.addressof(buf)
     lv = anchors.Level(Na=4, N0=4, k=2, F=3, scaling_stride=6, thr_lo=0.0, thr_hi=1.0, rand_thr=0.5, cell=0.1, origin=(C.c_float * 3)(0, 0, 0),

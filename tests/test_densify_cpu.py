@@ -114,7 +114,7 @@ def test_entry_points_validate_before_the_device():
     import ctypes as C
     import gsrast
     from gsrast import densify
-    L = densify._lib()
+    L = gsrast.lib()
     buf = (C.c_float * 64)()
     addr = C.addressof(buf)
 

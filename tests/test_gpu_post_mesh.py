@@ -195,7 +195,8 @@ def test_index_out_of_range_is_an_error_not_a_fault():
 
 def test_large_indices_through_the_c_abi():
     """Null vertices, V = 2^31 - 1: nothing of that size is allocated, the edge keys use all of their 62 bits."""
-    from gsrast import mesh, check, ptr, stream_ptr
+    import gsrast
+    from gsrast import check, ptr, stream_ptr
     _, _, t = cases.mixed_mesh(3000, seed=11)
     r = np.random.default_rng(12)
     nv = int(t.max()) + 1
@@ -207,7 +208,7 @@ def test_large_indices_through_the_c_abi():
     rc, rn, _ = ref.cluster_connected_triangles(big)
     assert np.array_equal(rn, ref.cluster_connected_triangles(t)[1])
     T, V = len(big), 2 ** 31 - 1
-    L = mesh._lib()
+    L = gsrast.lib()
     tris = torch.from_numpy(big).cuda()
     tc, cn = torch.empty(T, dtype=torch.int32, device="cuda"), torch.empty(T, dtype=torch.int32, device="cuda")
     nbytes = L.gsr_mesh_post_scratch_bytes(T, 0)

@@ -110,7 +110,7 @@ def test_argument_errors_of_the_c_abi_without_a_device():
     import ctypes as C
     import gsrast
     from gsrast import mesh
-    L = mesh._lib()
+    L = gsrast.lib()
     buf = (C.c_uint32 * 64)()
     a = C.addressof(buf)
     assert L.gsr_mesh_post_scratch_bytes(1 << 30, 10) == 0 and L.gsr_mesh_post_scratch_bytes(-1, 10) == 0           # 3T >= 2^31

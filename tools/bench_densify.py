@@ -22,6 +22,7 @@ import numpy as np      # noqa: E402
 import torch            # noqa: E402
 import densify_cases as DC          # noqa: E402
 import ref_densify_torch as R       # noqa: E402
+import gsrast                # noqa: E402
 from gsrast import densify   # noqa: E402
 
 HBM = 8.0e12
@@ -161,7 +162,7 @@ def main():
             ent["bytes_inputs"], ent["bytes_peak"], ent["bytes_outputs"] = before, peak, tensor_bytes(m)
             if tag == "hip":
                 rows = m._xyz.shape[0]
-                ent["bytes_scratch"] = int(densify._lib().gsr_densify_plan_scratch_bytes(P, 2)) + 32
+                ent["bytes_scratch"] = int(gsrast.lib().gsr_densify_plan_scratch_bytes(P, 2)) + 32
                 ent["bytes_activated_and_noise"] = P * 16 + 2 * P * 12            # get_scaling + get_opacity, and an upper bound of the draws
                 ent["peak_within_inputs_outputs_scratch"] = bool(peak <= before + ent["bytes_outputs"] + ent["bytes_scratch"] + ent["bytes_activated_and_noise"] + (1 << 20))
                 # algorithmic bytes of the copy: every output row written once; a parameter row read once, a moment row read only where it is carried

@@ -23,6 +23,7 @@ import numpy as np      # noqa: E402
 import torch            # noqa: E402
 import post_mesh_cases as PC        # noqa: E402
 import ref_post_mesh_numpy as R     # noqa: E402
+import gsrast                      # noqa: E402
 from gsrast import mesh as M        # noqa: E402
 from gsrast.tsdf import TriangleMesh   # noqa: E402
 
@@ -132,7 +133,7 @@ def main():
         torch.cuda.synchronize()
         row["bytes_inputs"], row["bytes_peak"] = int(before), int(torch.cuda.max_memory_allocated())
         row["bytes_outputs"] = int(sum(x.numel() * x.element_size() for x in (out.vertices, out.vertex_colors, out.triangles)))
-        row["bytes_scratch"] = int(M._lib().gsr_mesh_post_scratch_bytes(T, len(v)))
+        row["bytes_scratch"] = int(gsrast.lib().gsr_mesh_post_scratch_bytes(T, len(v)))
         # the host path: copy down, filter, (a user would then copy up or write the file from the host)
         t0 = time.perf_counter()
         hv, hc, ht = (x.cpu().numpy() for x in (m.vertices, m.vertex_colors, m.triangles))
