@@ -15,10 +15,20 @@
 #include "gsr_tile_sort.h"
 
 // =================================================================================================== forward
+// The pair loop's counter: one iteration fewer to go, none once no pixel of the wave blends any more (the early exit).  Two scalar instructions; as
+// `live ? left - 1 : 0` the compiler folds the exit into the loop condition as 64-bit selects, eleven scalar instructions an iteration.
+__device__ __forceinline__ uint32_t fwd_next_left(uint32_t left, uint64_t live)
+{
+    uint32_t r;
+    asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, %2, 0" : "=s"(r) : "s"(live), "s"(__builtin_amdgcn_readfirstlane((int)(left - 1u))) : "scc");
+    return r;
+}
+
 template <int V>
 __global__ void __launch_bounds__(256) k_blend_fwd(BlendParams p)
 {
     constexpr int ST = (V == GSR_EWA) ? GSR_REC_EWA : (V == GSR_PLANE ? GSR_REC_PLANE : GSR_REC_SURFEL);
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
     // [wave][record quarter][candidate slot]: private to the wave, no barrier.  20 KB for every variant (SURFEL needs them; eight workgroups per CU --
     // the wave limit -- fit either way): the sort prologue borrows the buffer and takes lists of up to 2048 entries in LDS instead of sending EWA's
     // beyond 1024 to the global-memory radix path (EWA at P = 1.5 M: 624 -> 663 it/s; neutral at 300k: blend forward 0.2207 vs 0.2204 ms)
@@ -111,12 +121,15 @@ __global__ void __launch_bounds__(256) k_blend_fwd(BlendParams p)
 #ifdef FWD_DIAG_NO_STAGE
         m = 0; if (lane == 99) s_rec[0] = make_float4(0.f, 0.f, 0.f, 0.f);
 #endif
-        while (m) {
-            const int j = __ffsll((unsigned long long)m) - 1;
-            m &= m - 1;
-            const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)id, j);
-            const uint32_t contributor = base - range.x + (uint32_t)j + 1u;
-            const float4* lr = s_rec + wave * ST * 64 + j;
+        // The slot a lane last blended, and the last one it blended at T > 0.5, are all the pair loop keeps of "which splat": the positions in the list and,
+        // for the median, the normal and the gaussian's id are looked up once per batch below, while the batch is still staged.
+        uint32_t slot_last = NONE, slot_med = NONE;
+        for (uint32_t left = (uint32_t)__popcll(m); left != 0u; left = fwd_next_left(left, live)) {
+            // the queue's next slot, and its removal: one scalar instruction each (as `m &= m - 1` the removal is three)
+            uint32_t sl;
+            asm("s_ff1_i32_b64 %0, %1" : "=s"(sl) : "s"(m));
+            asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(sl));
+            const float4* lr = s_rec + wave * ST * 64 + sl;
 #define FWD_LD(k) lr[(k) * 64]
             if (V != GSR_SURFEL) {
                 const float4 q0 = FWD_LD(0), q1 = FWD_LD(1), q2 = FWD_LD(2);
@@ -129,7 +142,7 @@ __global__ void __launch_bounds__(256) k_blend_fwd(BlendParams p)
                 live &= ~stopm; okm &= ~stopm;
                 if (V == GSR_PLANE) {
                     const uint64_t ob = okm & __builtin_amdgcn_fcmpf(T, 0.5f, 2);
-                    if (ob != 0 && lane == 0) atomicAdd(&p.out_observe[gid], (int)__popcll(ob));
+                    if (ob != 0 && lane == 0) atomicAdd(&p.out_observe[__builtin_amdgcn_readlane((int)id, (int)sl)], (int)__popcll(ob));
                 }
                 const bool ok = __builtin_amdgcn_inverse_ballot_w64(okm);
                 if (ok) {
@@ -140,7 +153,7 @@ __global__ void __launch_bounds__(256) k_blend_fwd(BlendParams p)
                         A0 += q2.y * w; A1 += q2.z * w; A2 += q2.w * w; A3 += q3.x * w; A4 += q3.y * w;
                     }
                     T = test_T;
-                    last_contributor = contributor;
+                    slot_last = sl;
                 }
             } else {
                 const float4 q0 = FWD_LD(0), q1 = FWD_LD(1), q2 = FWD_LD(2), q3 = FWD_LD(3), q4 = FWD_LD(4);
@@ -166,18 +179,26 @@ __global__ void __launch_bounds__(256) k_blend_fwd(BlendParams p)
                     const float mm = fmaf(-(FAR_N * NEAR_N) / (FAR_N - NEAR_N), rcp_(depth), FAR_N / (FAR_N - NEAR_N));      // far / (far - near) (1 - near / depth)
                     distortion += (mm * mm * A + M2 - 2 * mm * M1) * w;
                     Dd += depth * w; M1 += mm * w; M2 += mm * mm * w;
-                    if (T > 0.5f) {
-                        median_depth = depth; surf_idx = (int)gid;
-                        mn0 = q3.z; mn1 = q3.w; mn2 = q4.x;
-                        median_contributor = contributor;
-                    }
+                    if (T > 0.5f) { median_depth = depth; slot_med = sl; }
                     N0 += q3.z * w; N1 += q3.w * w; N2 += q4.x * w;
                     C0 += q4.y * w; C1 += q4.z * w; C2 += q4.w * w;
                     T = test_T;
-                    last_contributor = contributor;
+                    slot_last = sl;
                 }
             }
-            if (live == 0) break;
+        }
+        // per batch: slots -> positions in the tile's list (1-based), and the median splat's normal and id copied from its staged record and its lane
+        const uint32_t first = base - range.x + 1u;
+        if (slot_last != NONE) last_contributor = first + slot_last;
+        if (V == GSR_SURFEL) {
+            const int mid = __builtin_amdgcn_ds_bpermute((int)((slot_med & 63u) << 2), (int)id);      // lane slot_med's id; every lane takes part, only the lanes below use it
+            if (slot_med != NONE) {
+                const float4* mr = s_rec + wave * ST * 64 + (slot_med & 63u);
+                const float4 q3 = mr[3 * 64], q4 = mr[4 * 64];
+                mn0 = q3.z; mn1 = q3.w; mn2 = q4.x;
+                surf_idx = mid;
+                median_contributor = first + slot_med;
+            }
         }
     }
 
