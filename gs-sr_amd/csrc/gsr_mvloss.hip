@@ -29,6 +29,21 @@ __device__ __forceinline__ float3 mv_xform_t(const float* M, float3 d)      // d
     return make_float3(d.x * M[0] + d.y * M[1] + d.z * M[2], d.x * M[3] + d.y * M[4] + d.z * M[5], d.x * M[6] + d.y * M[7] + d.z * M[8]);
 }
 
+// exp(x) as a fixed sequence of float32 operations (Cody-Waite reduction by ln 2 in two parts, degree-7 polynomial on |r| <= 0.347, exact
+// scaling by 2^k), within ~1 ulp.  The library expf is within an ulp too, but its bits differ from one library to the next; with this one the
+// weight 1 / exp(noise) is the same bits here (built without contraction) as in the float32 oracle, which states the same sequence.
+__device__ __forceinline__ float mv_expf(float x)
+{
+    if (!(x < 100.f)) return x != x ? x : INFINITY;                        // overflow (the float32 limit is 88.7) and NaN
+    if (x < -110.f) return 0.f;
+    const float k = rintf(x * 1.44269504f);
+    const float r = (x - k * 0.693359375f) - k * -2.12194440e-4f;
+    float p = 1.9875691500e-4f;
+    p = p * r + 1.3981999507e-3f; p = p * r + 8.3334519073e-3f; p = p * r + 4.1665795894e-2f; p = p * r + 1.6666665459e-1f; p = p * r + 5.0000001201e-1f;
+    p = p * (r * r) + r + 1.f;
+    return ldexpf(p, (int)k);
+}
+
 __global__ void __launch_bounds__(256) k_mv_geo(gsr_mv_cfg c, const float* __restrict__ depth, const float* __restrict__ near_depth,
                                                 float* __restrict__ noise_out, uint8_t* __restrict__ dmask_out, float* __restrict__ weight_out,
                                                 float* __restrict__ g_depth, float* __restrict__ g_near, float2* __restrict__ partial)
@@ -64,7 +79,7 @@ __global__ void __launch_bounds__(256) k_mv_geo(gsr_mv_cfg c, const float* __res
         const float ex = r.x * c.fx / r.z + c.cx - (float)x, ey = r.y * c.fy / r.z + c.cy - (float)y;
         const float noise = sqrtf(ex * ex + ey * ey);
         const bool dm = mask && noise < c.noise_th;
-        const float w = dm ? 1.0f / expf(noise) : 0.f;
+        const float w = dm ? 1.0f / mv_expf(noise) : 0.f;
         noise_out[p] = noise; dmask_out[p] = dm ? 1 : 0; weight_out[p] = w;
         float gd = 0.f;
         if (dm) {

@@ -79,6 +79,24 @@ static float bilerp_zeros(const float* img, int W, int H, float u, float v, floa
     return val;
 }
 
+/* exp(x) as the kernel's mv_expf states it: the same float32 operations in the same order (csrc/gsr_mvloss.hip), so that the weight is the
+ * same bits in both (the plain build; the FMA twin contracts the reduction and the polynomial).  Within ~1 ulp of exp. */
+static float mv_expf(float x) {
+    if (!(x < 100.f)) return x != x ? x : INFINITY;
+    if (x < -110.f) return 0.f;
+    const float k = rintf(x * 1.44269504f);
+    const float r = (x - k * 0.693359375f) - k * -2.12194440e-4f;
+    float p = 1.9875691500e-4f;
+    p = p * r + 1.3981999507e-3f; p = p * r + 8.3334519073e-3f; p = p * r + 4.1665795894e-2f; p = p * r + 1.6666665459e-1f; p = p * r + 5.0000001201e-1f;
+    p = p * (r * r) + r + 1.f;
+    return ldexpf(p, (int)k);
+}
+
+/* mv_expf on n values, for the CPU test that holds it to float64 exp (tests/test_mv_truth_cpu.py) */
+void refm_mv_expf(int32_t n, const float* x, float* out) {
+    for (int i = 0; i < n; ++i) out[i] = mv_expf(x[i]);
+}
+
 void refm_multiview_geo(const refm_cfg* c, const float* depth, const float* near_depth, float* noise_out, uint8_t* dmask_out, float* weight_out,
                         double* stats, float* g_depth, float* g_near) {
     const int W = c->W, H = c->H, Wn = c->Wn, Hn = c->Hn;
@@ -100,7 +118,7 @@ void refm_multiview_geo(const refm_cfg* c, const float* depth, const float* near
             const float ex = r[0] * c->fx / r[2] + c->cx - (float)x, ey = r[1] * c->fy / r[2] + c->cy - (float)y;
             const float noise = sqrtf(ex * ex + ey * ey);
             const int dm = mask && noise < c->noise_th;
-            const float w = dm ? 1.0f / expf(noise) : 0.f;
+            const float w = dm ? 1.0f / mv_expf(noise) : 0.f;
             noise_out[p] = noise; dmask_out[p] = (uint8_t)dm; weight_out[p] = w;
             g_depth[p] = 0.f;
             if (!dm) continue;
@@ -199,6 +217,51 @@ void refm_multiview_ncc(const refm_cfg* c, int32_t N, const int32_t* idx, const 
         g_dist[p] = gd;
     }
     stats[0] = sum; stats[1] = (double)cnt;
+}
+
+/* The float32 intermediates that decide the gates, for tests/mv_truth.py to measure how far a float32 evaluation strays from float64:
+ * per pixel (u, v, q.z) exactly as refm_multiview_geo computes them; per sample and tap the warped coordinate (g.x/g.z, g.y/g.z) and g.z
+ * (with its 1e-10) exactly as refm_multiview_ncc does, taps in row-major patch order, unused slots untouched. */
+void refm_multiview_proj(const refm_cfg* c, const float* depth, float* u_out, float* v_out, float* qz_out) {
+    for (int y = 0; y < c->H; ++y)
+        for (int x = 0; x < c->W; ++x) {
+            const int p = y * c->W + x;
+            const float d = depth[p];
+            const float rx = ((float)x - c->cx) / c->fx, ry = ((float)y - c->cy) / c->fy;
+            float pc[3] = {rx * d, ry * d, d}, q[3];
+            xform(c->v2n, pc, q);
+            u_out[p] = q[0] * c->nfx / q[2] + c->ncx; v_out[p] = q[1] * c->nfy / q[2] + c->ncy; qz_out[p] = q[2];
+        }
+}
+
+void refm_multiview_warp(const refm_cfg* c, int32_t N, const int32_t* idx, const float* normal, const float* dist, float* out3) {
+    const int W = c->W, H = c->H, h = c->patch, ntap = (2 * h + 1) * (2 * h + 1);
+    const size_t HW = (size_t)W * H;
+    const float s = c->ncc_scale;
+    const float Kn[9] = {c->nfx / s, 0, c->ncx / s, 0, c->nfy / s, c->ncy / s, 0, 0, 1};
+    const float Kvi[9] = {s / c->fx, 0, -c->cx / c->fx, 0, s / c->fy, -c->cy / c->fy, 0, 0, 1};
+    for (int i = 0; i < N; ++i) {
+        const int p = idx[i];
+        if (p < 0) continue;
+        const int x = p % W, y = p / W;
+        const float n[3] = {normal[p], normal[HW + p], normal[2 * HW + p]}, dd = dist[p];
+        float Hm[9], T1[9], Hk[9];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) Hm[a * 3 + b] = c->v2n[b * 3 + a] - c->v2n[9 + a] * n[b] / dd;
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) T1[a * 3 + b] = Kn[a * 3 + 0] * Hm[0 * 3 + b] + Kn[a * 3 + 1] * Hm[1 * 3 + b] + Kn[a * 3 + 2] * Hm[2 * 3 + b];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) Hk[a * 3 + b] = T1[a * 3 + 0] * Kvi[0 * 3 + b] + T1[a * 3 + 1] * Kvi[1 * 3 + b] + T1[a * 3 + 2] * Kvi[2 * 3 + b];
+        const float px = (float)x / s, py = (float)y / s;
+        int j = 0;
+        for (int oy = -h; oy <= h; ++oy)
+            for (int ox = -h; ox <= h; ++ox, ++j) {
+                const float uu = px + (float)ox, vv = py + (float)oy;
+                const float g0 = Hk[0] * uu + Hk[1] * vv + Hk[2], g1 = Hk[3] * uu + Hk[4] * vv + Hk[5], g2 = Hk[6] * uu + Hk[7] * vv + Hk[8] + 1e-10f;
+                float* o = out3 + 3 * ((size_t)i * ntap + j);
+                o[0] = g0 / g2; o[1] = g1 / g2; o[2] = g2;
+            }
+    }
 }
 
 /*

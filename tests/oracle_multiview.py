@@ -65,6 +65,39 @@ def ncc(cfg, idx, weight, normal, dist, gray, near_gray):
     return out
 
 
+def proj(cfg, depth):
+    """-> (u, v, qz) float32 [W*H]: the projection into the neighbour exactly as refm_multiview_geo evaluates it"""
+    L = oracle.lib()
+    L.refm_multiview_proj.restype = None
+    d = _f(depth).reshape(-1)
+    out = [np.zeros(cfg.W * cfg.H, np.float32) for _ in range(3)]
+    L.refm_multiview_proj(C.byref(cfg), _p(d), *[_p(o) for o in out])
+    return out
+
+
+def warp(cfg, idx, normal, dist):
+    """-> float32 [N, ntap, 3]: warped tap coordinates (x, y) and the homography's third row g2, as refm_multiview_ncc evaluates them (NaN in
+    unused slots)"""
+    L = oracle.lib()
+    L.refm_multiview_warp.restype = None
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    ntap = (2 * cfg.patch + 1) ** 2
+    out = np.full((idx.size, ntap, 3), np.nan, np.float32)
+    nm, ds = _f(normal).reshape(-1), _f(dist).reshape(-1)
+    L.refm_multiview_warp(C.byref(cfg), C.c_int32(idx.size), idx.ctypes.data_as(C.c_void_p), _p(nm), _p(ds), _p(out))
+    return out
+
+
+def mv_expf(x):
+    """the oracle's (and the kernel's) exp: oracle/gsm_oracle.c mv_expf on a float32 array"""
+    L = oracle.lib()
+    L.refm_mv_expf.restype = None
+    x = _f(x).reshape(-1)
+    out = np.zeros(x.size, np.float32)
+    L.refm_mv_expf(C.c_int32(x.size), _p(x), _p(out))
+    return out
+
+
 def fixture_cfg(z):
     cam = lambda pre: {k: (z[f"{pre}_{k}"] if k in ("R", "T") else float(z[f"{pre}_{k}"])) for k in ("R", "T", "Fx", "Fy", "Cx", "Cy")}
     return make_cfg(int(z["W"]), int(z["H"]), cam("v"), cam("n"), noise_th=float(z["pixel_noise_threshold"]), patch=int(z["patch_size"]))

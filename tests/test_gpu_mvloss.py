@@ -47,11 +47,26 @@ def test_multiview_matches_oracle(kw):
     if cnt == 0:
         assert geo == 0.0 and ncc == 0.0 and not any(np.abs(v).max() for v in g.values())
         return
+    # the gradient checks are unconditional: a flipped gate takes out only what it feeds -- its own pixel, the four texels around its projection
+    # (a cell further for a coordinate that rounds across a cell edge), its term of the sum -- and everything else is still compared
+    dm_dev = aux["d_mask"].reshape(-1)
+    cnt_dev = int(dm_dev.sum())
+    assert cnt_dev == int(cnt) + int((flips & dm_dev).sum()) - int((flips & ~dm_dev).sum()) == int(aux["stats"][1])
+    wn = np.exp(-og["noise"].astype(np.float64)) * og["noise"]
+    np.testing.assert_allclose(geo, 0.03 * wn[dm_dev].sum() / cnt_dev, rtol=1e-4)
     if not flips.any():
         np.testing.assert_allclose(geo, 0.03 * og["stats"][0] / cnt, rtol=1e-4)
-        assert _rel(g["plane_depth"].reshape(-1) / 2.0, 0.03 / cnt * og["g_depth"]) < 1e-3
-        assert _rel(g["near_plane_depth"].reshape(-1) / 2.0, 0.03 / cnt * og["g_near"]) < 1e-3
-    # NCC on the oracle's own sample set and weights, so that it is compared independently of the geo gates
+    uo, vo, _ = om.proj(cfg, case["plane_depth"])
+    fed = np.zeros(W * H, bool)
+    for p in np.nonzero(flips)[0]:
+        x0, y0 = int(np.floor(min(max(uo[p], 0), W - 1))), int(np.floor(min(max(vo[p], 0), H - 1)))
+        fed.reshape(H, W)[max(y0 - 1, 0):y0 + 3, max(x0 - 1, 0):x0 + 3] = True
+    sg = 0.03 / cnt_dev
+    assert _rel(g["plane_depth"].reshape(-1)[~flips] / 2.0, sg * og["g_depth"][~flips]) < 1e-3
+    assert _rel(g["near_plane_depth"].reshape(-1)[~fed] / 2.0, sg * og["g_near"][~fed]) < 1e-3
+    assert not g["plane_depth"].reshape(-1)[~dm_dev].any()
+    # NCC on the oracle's own sample set, so that it is compared independently of the geo gates (the weights are the device's own: 0 where its
+    # d_mask flipped off)
     idx = np.nonzero(og["dmask"])[0].astype(np.int32)
     on = om.ncc(cfg, idx, og["weight"], case["rendered_normal"], case["rendered_distance"], case["gray"], case["near_gray"])
     geo2, ncc2, aux2, g2 = _run_hip(case, indices=idx)
@@ -60,8 +75,21 @@ def test_multiview_matches_oracle(kw):
     # Per-tap arithmetic follows the oracle's operation order (true divisions, same bilinear accumulation, -ffp-contract=off); the patch
     # sums are 16-lane butterflies instead of a sequential walk.  ncc = 1 - cross^2/(var var) is ill-conditioned on low-contrast patches
     # (the variances cancel to ~1e-3 of the float32 sums), where the summation order alone moves it by ~1e-3: bulk tight, tail loose.
+    # (tests/test_gpu_mvloss_edges.py holds every sample to its own kappa-scaled bound against float64.)
     e = np.abs(aux2["ncc"][~mflip] - on["ncc"][~mflip])
     assert np.quantile(e, 0.5) < 2e-5 and np.quantile(e, 0.99) < 2e-3 and e.max() < 3e-2, (np.quantile(e, 0.5), np.quantile(e, 0.99), e.max())
+    nm_dev = aux2["ncc_mask"]
+    ncnt = int(nm_dev.sum())
+    assert ncnt == int(on["stats"][1]) + int((mflip & nm_dev).sum()) - int((mflip & ~nm_dev).sum()) == int(aux2["stats"][4])
+    if ncnt > 0:
+        w_dev = aux2["weights"].reshape(-1)[idx].astype(np.float64)
+        np.testing.assert_allclose(ncc2, 0.15 * (on["ncc"].astype(np.float64) * w_dev)[nm_dev].sum() / ncnt, rtol=1e-4)
+        sc = 0.15 / ncnt
+        keep = np.ones(W * H, bool)
+        keep[idx[mflip | flips[idx]]] = False                                # a sample whose mask or whose pixel's weight flipped
+        assert _rel((g2["rendered_normal"].reshape(3, -1) / 3.0)[:, keep], sc * on["g_normal"][:, keep]) < 5e-3       # conditioning as above
+        assert _rel((g2["rendered_distance"].reshape(-1) / 3.0)[keep], sc * on["g_dist"][keep]) < 5e-3
+    # the earlier, conditional form alongside: with at most two flipped samples and no flipped pixel the WHOLE tensors against the oracle's own mean and count
     if on["stats"][1] > 0 and mflip.sum() <= 2 and not flips.any():
         np.testing.assert_allclose(ncc2, 0.15 * on["stats"][0] / on["stats"][1], rtol=1e-4)
         sc = 0.15 / on["stats"][1]
@@ -183,7 +211,14 @@ def test_multiview_other_patch_sizes(patch):
     assert mflip.sum() <= max(2, int(1e-3 * idx.size))
     e = np.abs(aux["ncc"][~mflip] - on["ncc"][~mflip])
     assert np.quantile(e, 0.5) < 2e-5 and np.quantile(e, 0.99) < 2e-3, (np.quantile(e, 0.5), np.quantile(e, 0.99))
-    if mflip.sum() <= 2:
+    ncnt = int(aux["ncc_mask"].sum())                                        # unconditional: a flipped sample takes out only its own pixel
+    assert ncnt > 0 and ncnt == int(aux["stats"][4])
+    sc = 0.15 / ncnt
+    dflip = aux["d_mask"].reshape(-1)[idx] != og["dmask"][idx].astype(bool)
+    keep = np.ones(96 * 64, bool); keep[idx[mflip | dflip]] = False
+    assert _rel((g["rendered_normal"].reshape(3, -1) / 3.0)[:, keep], sc * on["g_normal"][:, keep]) < 5e-3
+    assert _rel((g["rendered_distance"].reshape(-1) / 3.0)[keep], sc * on["g_dist"][keep]) < 5e-3
+    if mflip.sum() <= 2:                                                     # the earlier, conditional form alongside: the whole tensors, the oracle's count
         sc = 0.15 / on["stats"][1]
         assert _rel(g["rendered_normal"].reshape(3, -1) / 3.0, sc * on["g_normal"]) < 5e-3
         assert _rel(g["rendered_distance"].reshape(-1) / 3.0, sc * on["g_dist"]) < 5e-3
