@@ -385,7 +385,7 @@ __global__ void __launch_bounds__(256) k_surfel_geo(GeoArgs p)
         const float a0 = p.allmap[o], a = p.allmap[N + o], m = p.allmap[5 * N + o], q = a0 / a;
         const bool okq = !(isnan(q) || isinf(q)), okm = !(isnan(m) || isinf(m));
         p.dL[o] = okq ? dd * (1.0f - p.depth_ratio) / a : 0.0f;
-        p.dL[N + o] = okq ? -dd * (1.0f - p.depth_ratio) * a0 / (a * a) : 0.0f;
+        p.dL[N + o] = okq ? -dd * (1.0f - p.depth_ratio) * q / a : 0.0f;          // not a0 / (a * a): a * a underflows below alpha = 2^-63
         p.dL[5 * N + o] = okm ? dd * p.depth_ratio : 0.0f;
         const float s0 = sN[0][qy][qx], s1 = sN[1][qy][qx], s2 = sN[2][qy][qx];
 #pragma unroll
@@ -488,8 +488,14 @@ __global__ void __launch_bounds__(256) k_plane_geo(PlaneGeoArgs p)
             const float a = p.alpha[o], wl = p.wl * (p.weight ? p.weight[o] : 1.0f);
             float dx[3], dy[3], dn[3], len, inv;
             geo_stencil(sP, ly + 1, lx + 1, dx, dy, n, len, inv);
+            // the sign of the ROUNDED product minus the normal, as the third phase takes it from sN (contracted into an fma this is the sign of the
+            // exact difference: within half an ulp dL_ddepth was routed with a sign that the value and dL_dnormal did not have)
 #pragma unroll
-            for (int c = 0; c < 3; c++) dn[c] = wl * a * sgn_(a * n[c] - p.normal[c * N + o]);
+            for (int c = 0; c < 3; c++) {
+#pragma clang fp contract(off)
+                const float sn = n[c] * a;
+                dn[c] = wl * a * sgn_(sn - p.normal[c * N + o]);
+            }
             geo_stencil_adjoint(dn, n, len, inv, dx, dy, g);
             n[0] *= a; n[1] *= a; n[2] *= a;
         }

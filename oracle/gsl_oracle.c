@@ -171,7 +171,7 @@ void ref_loss_surfel_geo(int32_t H, int32_t W, const float* allmap, const float*
             const float a = allmap[N + o], q = allmap[o] / a;
             if (!(isnan(q) || isinf(q))) {
                 dL_dallmap[o] += dd * (1.f - depth_ratio) / a;
-                dL_dallmap[N + o] += -dd * (1.f - depth_ratio) * allmap[o] / (a * a);
+                dL_dallmap[N + o] += -dd * (1.f - depth_ratio) * q / a;      /* not allmap[o] / (a * a): a * a underflows below alpha = 2^-63 */
             }
             const float m = allmap[5 * N + o];
             if (!(isnan(m) || isinf(m))) dL_dallmap[5 * N + o] += dd * depth_ratio;
