@@ -205,6 +205,13 @@ FUNCTIONS = [
     ("gsr_voxel_unique_emit", cint, [vp, i64, i32, P(f64), P(f64), i32, vp, sz, P(u32), vp, vp, vp]),
     ("gsr_view_select_scratch_bytes", sz, [i64, i32]),
     ("gsr_view_select", cint, [vp, i32, vp, vp, i64, vp, vp, i64, f64, f64, f64, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
+    ("gsr_partition_boxes", cint, [vp, i64, i32, vp, i32, vp, vp, vp, vp]),
+    ("gsr_partition_zrange_scratch_bytes", sz, [i64, i64]),
+    ("gsr_partition_zrange", cint, [vp, i64, vp, i32, i32, i64, i64, vp, vp, vp, sz, vp, vp]),
+    ("gsr_partition_visibility", cint, [vp, vp, i32, vp, vp, vp, i32, vp, f64, vp, vp, vp, vp, vp, vp]),
+    ("gsr_partition_coverage_mask", cint, [vp, vp, i64, vp, i32, vp, i64, i32, vp, vp, vp, vp]),
+    ("gsr_partition_coverage_rows_scratch_bytes", sz, [i64]),
+    ("gsr_partition_coverage_rows", cint, [vp, i64, i32, P(i64), vp, vp, sz, vp]),
     ("gsr_debug_read", cint, [_cfg, i32, vp, vp, sz, vp, u32, vp, vp]),
     ("gsr_profile_enable", cint, [i32]),
     ("gsr_profile_read", cint, [P(f64), P(u64)]),

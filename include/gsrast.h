@@ -739,6 +739,50 @@ int gsr_view_select(const double* centres /*[C,3]*/, int32_t C, const int64_t* o
                     int32_t k, int32_t id_bits, int32_t* near_ids /*[C,k]*/, double* near_scores /*[C,k]*/, double* scores /*[C,C] or NULL*/,
                     void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[1]*/, void* stream);
 
+/* ---- scene partition (VastGaussian tiles: split_scene.py:39-53, gssr/utils/vastgaussian_utils.py:150-286; additions, no ABI bump).
+ * T <= GSR_PART_MAX_TILES tiles (their boxes and counters are held in LDS); a tile mask is W = ceil(T / 32) words per row, bit t & 31 of word t >> 5.
+ * N, M, Np < 2^31.  Everything is float64 unless said otherwise.  *status_dev carries GSR_PART_ERR_* bits afterwards; the host wrapper reads it and raises.
+ * gsr_partition_boxes: mask [N,W] and counts [T] of the rows (x, y = the first two of `stride` doubles) inside boxes [T,4] = (mx, Mx, my, My), bounds
+ *   included, compared in float64.  One pass over the rows whatever T.  A NaN coordinate is in no box; a NaN bound sets NONFINITE.  Clears status and counts.
+ * gsr_partition_zrange: for ONE tile, count = the rows of xyz [N,3] whose bit is set (the caller knows it from counts; n_max >= count sizes the scratch):
+ *   their float32 xyz compacted, gsr_dist2 on that subset, mean and population std of the distances in float64 in a fixed order (stats [T,2], row
+ *   `tile`), and zrange [T,2] row `tile` = min and max of float32 z over mean - 3 std < dist < mean + 3 std (strict).  count < 4, or no distance inside,
+ *   sets FEW; a coordinate that is not finite as float32, or a non-finite threshold, NONFINITE; count != the bits of the mask, COUNT.  *status_dev is
+ *   NOT cleared: the caller clears it once and calls per tile.
+ * gsr_partition_visibility: md [T] = 1.2 x the mean over tile t's member images (member [C,W]) of the largest Euclidean distance from the centre to
+ *   the eight corners of (box t, zrange t); then per (t, c), row-major [T,C]: the corners through w2c [C,12] (rows of [R | t]) and K = (fx, fy, width / 2,
+ *   height / 2) from intr [C,4] = (fx, fy, width, height), no test of the sign of z; ratio = area(hull of the eight projections, clipped to
+ *   [0, width] x [0, height]) / (width height); dist = the mean over the corners of |dx| + |dy| + |dz| to centres [C,3]; add = ratio > threshold and
+ *   dist < md[t] and c is no member of t.  A hull of zero area gives ratio 0.  A corner with camera-space z == 0 sets ZERO_Z, a non-finite term NONFINITE.
+ * gsr_partition_coverage_mask: point_mask [Np,W] = OR over the observations (image a in [obs_offsets[a], obs_offsets[a + 1]), id != -1) of
+ *   image_mask [C,W] row a into the row of point_ids [Np] (ascending strictly) that holds the id; counts [T] = rows per tile.  An id absent from
+ *   point_ids that an image of at least one tile observes sets ABSENT.  TABLE / OFFSETS as for the neighbour views.  Clears status, counts, point_mask.
+ * gsr_partition_coverage_rows: rows [tile_offsets[T]] = per tile t, at tile_offsets[t] (HOST, the exclusive prefix of counts), the rows of point_mask
+ *   with bit t, ascending: one compaction per tile. */
+#define GSR_PART_MAX_TILES 1024
+#define GSR_PART_BLOCK 256
+#define GSR_PART_ERR_FEW 1u
+#define GSR_PART_ERR_NONFINITE 2u
+#define GSR_PART_ERR_ZERO_Z 4u
+#define GSR_PART_ERR_ABSENT 8u
+#define GSR_PART_ERR_TABLE 16u
+#define GSR_PART_ERR_OFFSETS 32u
+#define GSR_PART_ERR_COUNT 64u
+int gsr_partition_boxes(const double* xyz /*[N,stride]*/, int64_t N, int32_t stride, const double* boxes /*[T,4]*/, int32_t T, uint32_t* mask /*[N,W]*/,
+                        uint32_t* counts /*[T]*/, uint32_t* status_dev /*[1]*/, void* stream);
+size_t gsr_partition_zrange_scratch_bytes(int64_t N, int64_t n_max);
+int gsr_partition_zrange(const double* xyz /*[N,3]*/, int64_t N, const uint32_t* mask /*[N,W]*/, int32_t T, int32_t tile, int64_t count, int64_t n_max,
+                         float* zrange /*[T,2]*/, double* stats /*[T,2]*/, void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[1]*/, void* stream);
+int gsr_partition_visibility(const double* boxes /*[T,4]*/, const float* zrange /*[T,2]*/, int32_t T, const double* w2c /*[C,12]*/, const double* centres /*[C,3]*/,
+                             const double* intr /*[C,4]*/, int32_t C, const uint32_t* member /*[C,W]*/, double threshold, double* ratio /*[T,C]*/,
+                             double* dist /*[T,C]*/, double* md /*[T]*/, uint8_t* add /*[T,C]*/, uint32_t* status_dev /*[1]*/, void* stream);
+int gsr_partition_coverage_mask(const int64_t* obs_offsets /*[C + 1]*/, const int64_t* obs_ids /*[M]*/, int64_t M, const uint32_t* image_mask /*[C,W]*/, int32_t C,
+                                const int64_t* point_ids /*[Np]*/, int64_t Np, int32_t T, uint32_t* point_mask /*[Np,W]*/, uint32_t* counts /*[T]*/,
+                                uint32_t* status_dev /*[1]*/, void* stream);
+size_t gsr_partition_coverage_rows_scratch_bytes(int64_t Np);
+int gsr_partition_coverage_rows(const uint32_t* point_mask /*[Np,W]*/, int64_t Np, int32_t T, const int64_t* tile_offsets /*host [T + 1]*/, int64_t* rows,
+                                void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
