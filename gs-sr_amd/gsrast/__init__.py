@@ -70,8 +70,96 @@ def check(rc, what):
         raise RuntimeError(f"gsrast {what}: {last_error()}")
 
 
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)      # private, but what torch's own generated code reads the stream with
+
+
 def stream_ptr(device=None):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    """The current stream of `device` (None: of the current device) as a pointer.  Read through torch's raw-stream getter where this torch has
+    it: torch.cuda.current_stream() builds a Stream object per call, 2 us of a 7 us call (EXPERIMENTS.md (94)); it is the fallback."""
+    if device is not None and not isinstance(device, torch.device):
+        device = torch.device(device)
+    if _raw_stream is None:
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    index = None if device is None else device.index
+    if index is None:
+        index = torch.cuda.current_device()
+    return C.c_void_p(_raw_stream(index))
+
+
+# ---- the gate: the one place that knows how a call into the library is made.  Every entry point that enqueues work takes its stream last
+# (_abi.FUNCTIONS: restype cint, last argtype vp); the library launches on that stream and keeps per-device state under hipGetDevice(), so the
+# tensors' device must be the current one while the call runs, and every pointer must lie on it.
+def enqueue(name, dev, *args):
+    """-> rc of entry point `name`, called with `dev` current (made so for the call where it is not) and stream_ptr(dev) appended.  A torch.Tensor
+    among args must be contiguous and on `dev` and travels as its data pointer; None stays None; everything else (numbers, ctypes arrays and
+    structs, byref(), raw c_void_p) is passed as it is.  The entry point is looked up only once the arguments have passed.  Tensors whose
+    pointers sit inside a struct are invisible here: their caller holds them to one device with one_device()."""
+    current = torch.cuda.current_device()
+    if dev.index is None and dev.type == "cuda":
+        dev = torch.device("cuda", current)
+    argv = list(args)
+    for i, a in enumerate(argv):
+        if isinstance(a, torch.Tensor):
+            if a.device != dev:
+                raise RuntimeError(f"gsrast {name}: argument {i} is a tensor on {a.device}, the call runs on {dev}")
+            if not a.is_contiguous():
+                raise RuntimeError(f"gsrast {name}: argument {i} is not contiguous")
+            argv[i] = C.c_void_p(a.data_ptr())
+    fn = getattr(lib(), name)
+    if dev.index == current:                              # the common case, without the cost of entering and leaving the context
+        return fn(*argv, stream_ptr(dev))
+    with torch.cuda.device(dev):
+        return fn(*argv, stream_ptr(dev))
+
+
+def call(name, dev, *args, what=None):
+    """enqueue(), then check(): `what` labels the error where it is not the entry point's name without its gsr_ / gsd_ prefix."""
+    check(enqueue(name, dev, *args), what or name[4:])
+
+
+def scratch(nbytes, dev):
+    """A scratch block for a *_scratch_bytes figure: never empty, so that its pointer is never null."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def one_device(*named):
+    """(name, tensor or None) pairs -> the device of the first tensor; every other one must share it.  For tensors that reach the library inside
+    a struct, where enqueue() cannot see them."""
+    first = dev = None
+    for name, t in named:
+        if t is None:
+            continue
+        if dev is None:
+            first, dev = name, t.device
+        elif t.device != dev:
+            raise RuntimeError(f"{name} must be on the device of {first}")
+    return dev
+
+
+def status_text(op, word, table):
+    """The text of a status word a kernel left: `table` is {bit: text}."""
+    parts = [text for bit, text in table.items() if word & bit]
+    return f"gsrast {op}: status {word}: " + "; ".join(parts or ["unknown bits"])
+
+
+def raise_status(op, word, table):
+    if word:
+        raise RuntimeError(status_text(op, word, table))
+
+
+def typed_tensor(t, name, dtype, shape, device=None):
+    """A contiguous HIP tensor of `dtype` and `shape` (None: any size, printed as '*'), optionally on `device`, or a RuntimeError that names it."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name}: expected {dtype} but found {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
+        raise RuntimeError(f"{name}: expected shape {[s if s is not None else '*' for s in shape]} but found {list(t.shape)}")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"{name} must be on the device of {device}")
+    return t.detach().contiguous()
 
 
 def dev_f32(t, name, allow_empty=True):

@@ -5,7 +5,7 @@ three parameter tensors: three torch kernels forward (normalize alone is three) 
 Here: one streaming HIP kernel each way."""
 import torch
 
-from . import check, dev_f32, lib, ptr, stream_ptr
+from . import call, dev_f32
 
 
 class _GaussActivations(torch.autograd.Function):
@@ -18,7 +18,7 @@ class _GaussActivations(torch.autograd.Function):
         if s.dim() != 2 or not (1 <= s.shape[1] <= 3) or q.shape != (P, 4) or o.numel() != P:
             raise RuntimeError("gaussian_activations: scaling (P, 1..3), rotation (P, 4), opacity (P, 1) expected")
         so, qo, oo = torch.empty_like(s), torch.empty_like(q), torch.empty_like(o)
-        check(lib().gsr_gauss_activations(P, int(s.shape[1]), ptr(s), ptr(q), ptr(o), ptr(so), ptr(qo), ptr(oo), stream_ptr(s.device)), "gauss_activations")
+        call("gsr_gauss_activations", s.device, P, int(s.shape[1]), s, q, o, so, qo, oo)
         ctx.save_for_backward(so, q, qo, oo)
         ctx.set_materialize_grads(False)
         return so, qo, oo
@@ -30,8 +30,7 @@ class _GaussActivations(torch.autograd.Function):
         c = lambda g: None if g is None else g.contiguous()
         gs, gq, go = c(gs), c(gq), c(go)
         ds, dq, do = torch.empty_like(so), torch.empty_like(q), torch.empty_like(oo)
-        check(lib().gsr_gauss_activations_backward(P, int(so.shape[1]), ptr(so), ptr(q), ptr(qo), ptr(oo), ptr(gs), ptr(gq), ptr(go), ptr(ds), ptr(dq), ptr(do),
-                                                   stream_ptr(so.device)), "gauss_activations_backward")
+        call("gsr_gauss_activations_backward", so.device, P, int(so.shape[1]), so, q, qo, oo, gs, gq, go, ds, dq, do)
         return ds, dq, do
 
 

@@ -20,7 +20,7 @@ import math
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, one_device, ptr, scratch
 from ._rows import Level, RowsTensor, _bytes, _f32, groups, install_, make_weed, moments
 
 PARAM_ATTRS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
@@ -76,33 +76,28 @@ def _grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cel
         raise RuntimeError(f"cell: expected a positive finite number but found {cell}")
     if len(origin) != 3:
         raise RuntimeError("origin: expected three numbers")
-    for name, t in (("offset", offset), ("scaling", scaling), ("anchor_feat", anchor_feat), ("grads", grads), ("rand", rand)):
-        if t is not None and t.device != anchor.device:
-            raise RuntimeError(f"{name} must be on the device of anchor")
+    dev = one_device(("anchor", anchor), ("offset", offset), ("scaling", scaling), ("anchor_feat", anchor_feat), ("grads", grads), ("rand", rand))
     if Na + N0 * k >= 1 << 31:
         raise RuntimeError(f"anchor: Na + n0 * k = {Na + N0 * k} entries exceed 2^31")
     L = lib()
-    dev = anchor.device
     lv = Level(Na, N0, k, F, scaling.shape[1], thr_lo, thr_hi, rand_thr, cell, (C.c_float * 3)(*[float(o) for o in origin]),
                ptr(anchor).value, None if mask is None else ptr(mask).value, ptr(offset).value, ptr(scaling).value, ptr(anchor_feat).value, ptr(grads).value,
                ptr(offset_mask).value, None if rand is None else ptr(rand).value)
-    with torch.cuda.device(dev):
-        nbytes = L.gsr_anchor_level_scratch_bytes(Na, N0, k)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        status = torch.zeros(3, dtype=torch.int32, device=dev)
-        if occupy is None and weed is None:
-            check(L.gsr_anchor_level_find(C.byref(lv), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)), "anchor_level_find")
-        else:
-            check(L.gsr_anchor_level_find_weed(C.byref(lv), ptr(occupy), None if weed is None else C.byref(weed), ptr(scratch), nbytes, ptr(status),
-                                               stream_ptr(dev)), "anchor_level_find_weed")
-        count, overflow, found = status.tolist()              # the level's one host synchronisation
-        if overflow:
-            raise RuntimeError(f"gsrast anchor growing: a candidate cell lies outside the packing range of +-2^20 cells per axis "
-                               f"(cell size {cell:g}: about +-{cell * (1 << 20):g} scene units around the origin)")
-        new_anchor = torch.empty(count, 3, dtype=torch.float32, device=dev)
-        new_feat = torch.empty(count, F, dtype=torch.float32, device=dev)
-        if count:
-            check(L.gsr_anchor_level_emit(C.byref(lv), ptr(scratch), nbytes, count, ptr(new_anchor), ptr(new_feat), stream_ptr(dev)), "anchor_level_emit")
+    nbytes = L.gsr_anchor_level_scratch_bytes(Na, N0, k)
+    work = scratch(nbytes, dev)
+    status = torch.zeros(3, dtype=torch.int32, device=dev)
+    if occupy is None and weed is None:
+        call("gsr_anchor_level_find", dev, C.byref(lv), work, nbytes, status)
+    else:
+        call("gsr_anchor_level_find_weed", dev, C.byref(lv), occupy, None if weed is None else C.byref(weed), work, nbytes, status)
+    count, overflow, found = status.tolist()              # the level's one host synchronisation
+    if overflow:
+        raise RuntimeError(f"gsrast anchor growing: a candidate cell lies outside the packing range of +-2^20 cells per axis "
+                           f"(cell size {cell:g}: about +-{cell * (1 << 20):g} scene units around the origin)")
+    new_anchor = torch.empty(count, 3, dtype=torch.float32, device=dev)
+    new_feat = torch.empty(count, F, dtype=torch.float32, device=dev)
+    if count:
+        call("gsr_anchor_level_emit", dev, C.byref(lv), work, nbytes, count, new_anchor, new_feat)
     return new_anchor, new_feat, (found if (occupy is not None or weed is not None) else count)
 
 
@@ -188,19 +183,18 @@ def rows_compact(keep, tensors, tails=None):
     L = lib()
     dev = keep.device
     n_keep = int(keep.count_nonzero()) if N else 0
-    with torch.cuda.device(dev):
-        nbytes = L.gsr_rows_compact_scratch_bytes(N)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        table = (RowsTensor * len(srcs))()
-        outs, n = [], 0
-        for x, rb, t in srcs:
-            nt = t.shape[0] if isinstance(t, torch.Tensor) else int(t or 0)
-            out = torch.empty((n_keep + nt,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
-            outs.append(out)
-            if out.numel():                                      # nothing kept and no tail: nothing to write
-                table[n] = RowsTensor(x.data_ptr() if N else None, out.data_ptr(), t.data_ptr() if isinstance(t, torch.Tensor) and nt else None, rb, nt)
-                n += 1
-        check(L.gsr_rows_compact_multi(N, ptr(keep) if N else None, n, table, ptr(scratch), nbytes, stream_ptr(dev)), "rows_compact_multi")
+    nbytes = L.gsr_rows_compact_scratch_bytes(N)
+    work = scratch(nbytes, dev)
+    table = (RowsTensor * len(srcs))()
+    outs, n = [], 0
+    for x, rb, t in srcs:
+        nt = t.shape[0] if isinstance(t, torch.Tensor) else int(t or 0)
+        out = torch.empty((n_keep + nt,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
+        outs.append(out)
+        if out.numel():                                      # nothing kept and no tail: nothing to write
+            table[n] = RowsTensor(x.data_ptr() if N else None, out.data_ptr(), t.data_ptr() if isinstance(t, torch.Tensor) and nt else None, rb, nt)
+            n += 1
+    call("gsr_rows_compact_multi", dev, N, keep if N else None, n, table, work, nbytes)
     return outs
 
 
@@ -357,6 +351,7 @@ def octree_adjust_anchor_(model, iteration, check_interval=100, success_threshol
         is_l = lvl == l
         cur = torch.cat((anchor, prev_b)) if prev_b is not None else anchor
         w, cams = make_weed(model.cam_infos, standard_dist, fork, levels, model.dist2level, visible_threshold, lv=l)
+        one_device(("model._anchor", anchor), ("model.cam_infos", cams))
         a, f, found = _grow_level(cur, model._offset, scaling, model._anchor_feat, grads, offset_mask, cell=cur_size, thr_lo=cur_thr, thr_hi=ds_thr, mask=is_l,
                                   occupy=is_l, origin=origin, n0=N0, weed=w)
         if trace is not None:

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from . import check, dev_f32, lib, ptr, stream_ptr
+from . import call, dev_f32, lib, one_device, ptr, scratch
 from ._abi import FUNCTIONS
 from ._abi import gsd_cfg as Cfg, gsd_inputs as Inputs, gsd_params as Params, gsd_outputs as Outputs, gsd_out_grads as OutGrads, gsd_in_grads as InGrads
 
@@ -29,12 +29,12 @@ def compact_visible(visible_mask, padded=False):
     Na = m.numel()
     L = lib()
     idx = torch.empty(Na, dtype=torch.int32, device=m.device)
-    scratch = torch.empty(L.gsd_compact_scratch_bytes(Na), dtype=torch.uint8, device=m.device)
+    work = scratch(L.gsd_compact_scratch_bytes(Na), m.device)
     if padded:
-        check(L.gsd_compact_visible_padded(ptr(m), Na, ptr(idx), None, ptr(scratch), scratch.numel(), stream_ptr(m.device)), "compact_visible")
+        call("gsd_compact_visible_padded", m.device, m, Na, idx, None, work, work.numel(), what="compact_visible")
         return idx
     n = C.c_uint32(0)
-    check(L.gsd_compact_visible(ptr(m), Na, ptr(idx), C.byref(n), ptr(scratch), scratch.numel(), stream_ptr(m.device)), "compact_visible")
+    call("gsd_compact_visible", m.device, m, Na, idx, C.byref(n), work, work.numel())
     return idx[: n.value]
 
 
@@ -43,6 +43,7 @@ def _structs(flags, Na, Nv, tensors, params):
     cfg = Cfg(Na, Nv, k, A, int(dist_o), int(dist_c), int(dist_k), int(has_level))
     inp = Inputs(*[ptr(tensors[n]) for n in ("anchor", "feat", "offset", "scaling", "level", "opacity_scale", "vis_idx", "campos")])
     prm = Params(*[ptr(params[n]) for n in PARAM_NAMES])
+    one_device(*tensors.items(), *params.items())
     return cfg, inp, prm
 
 
@@ -67,28 +68,27 @@ def _decode_launch(flags, t, prm, mode):
     cfg, inp, cp = _structs(flags, Na, Nv, t, prm)
     b = {"nop": torch.empty(Nv * k, 1, dtype=torch.float32, device=dev), "mask": torch.empty(Nv * k, dtype=torch.uint8, device=dev),
          "row_offset": torch.empty(max(Nv, 1), dtype=torch.int32, device=dev),
-         "scratch": torch.empty(L.gsd_forward_scratch_bytes(Nv), dtype=torch.uint8, device=dev), "count": None}
+         "scratch": scratch(L.gsd_forward_scratch_bytes(Nv), dev), "count": None}
     cap = Nv * k              # worst case: every offset emitted -> stage 2 is enqueued without waiting for the host to learn P
     b["out"] = [torch.empty(cap, c, dtype=torch.float32, device=dev) for c in (3, 3, 1, 3, 4)]       # xyz, color, opacity, scaling, rot
     out = Outputs(*[ptr(x) for x in b["out"]])
     if mode == "sync":
         P = C.c_uint32(0)
-        check(L.gsd_forward(C.byref(cfg), C.byref(inp), C.byref(cp), ptr(b["nop"]), ptr(b["mask"]), ptr(b["row_offset"]), C.byref(out), C.byref(P),
-                            ptr(b["scratch"]), b["scratch"].numel(), stream_ptr(dev)), "decode forward")
+        call("gsd_forward", dev, C.byref(cfg), C.byref(inp), C.byref(cp), b["nop"], b["mask"], b["row_offset"], C.byref(out), C.byref(P), b["scratch"],
+             b["scratch"].numel(), what="decode forward")
         b["n"] = P.value
         return b
     if mode == "deferred":    # the count leaves for pinned memory right behind stage 1; the event is recorded there, stage 2 follows (gsd_forward_deferred)
         b["slot"] = _count_slot(dev)
         b["count_host"], b["event"] = b["slot"]
-        check(L.gsd_forward_deferred(C.byref(cfg), C.byref(inp), C.byref(cp), ptr(b["nop"]), ptr(b["mask"]), ptr(b["row_offset"]), C.byref(out),
-                                     b["count_host"].data_ptr(), b["event"].cuda_event, ptr(b["scratch"]), b["scratch"].numel(), stream_ptr(dev)),
-              "decode forward (deferred count)")
+        call("gsd_forward_deferred", dev, C.byref(cfg), C.byref(inp), C.byref(cp), b["nop"], b["mask"], b["row_offset"], C.byref(out),
+             b["count_host"].data_ptr(), b["event"].cuda_event, b["scratch"], b["scratch"].numel(), what="decode forward (deferred count)")
         b["n"] = cap
         b["t"], b["prm"] = t, prm
         return b
     b["count"] = torch.empty(1, dtype=torch.int32, device=dev)
-    check(L.gsd_forward_static(C.byref(cfg), C.byref(inp), C.byref(cp), ptr(b["nop"]), ptr(b["mask"]), ptr(b["row_offset"]), C.byref(out), ptr(b["count"]),
-                               ptr(b["scratch"]), b["scratch"].numel(), stream_ptr(dev)), "decode forward (static rows)")
+    call("gsd_forward_static", dev, C.byref(cfg), C.byref(inp), C.byref(cp), b["nop"], b["mask"], b["row_offset"], C.byref(out), b["count"], b["scratch"],
+         b["scratch"].numel(), what="decode forward (static rows)")
     b["n"] = cap
     return b
 
@@ -161,13 +161,13 @@ class _NeuralDecode(torch.autograd.Function):
         else:
             t, prm = _decode_inputs(vis_idx, campos, level, opacity_scale, anchor, feat, offset, scaling, params)
             b = _decode_launch(flags, t, prm, "static" if static_rows else "sync")
-        nop, mask, row_offset, scratch, count, n = b["nop"], b["mask"], b["row_offset"], b["scratch"], b["count"], b["n"]
+        nop, mask, row_offset, work, count, n = b["nop"], b["mask"], b["row_offset"], b["scratch"], b["count"], b["n"]
         xyz, color, opacity, scl, rot = b["out"]
         if not static_rows:
             xyz, color, opacity, scl, rot = xyz[:n], color[:n], opacity[:n], scl[:n], rot[:n]
         ctx.flags, ctx.n = flags, n
         ctx.save_for_backward(t["anchor"], t["feat"], t["offset"], t["scaling"], t["level"], t["opacity_scale"], t["vis_idx"], t["campos"],
-                              nop, row_offset, scratch, *[prm[nm] for nm in PARAM_NAMES])
+                              nop, row_offset, work, *[prm[nm] for nm in PARAM_NAMES])
         mask_b = mask.view(torch.bool)
         ctx.set_materialize_grads(False)     # no zero-filled (Nv*k) gradient tensors for nop / mask (or an unused output) on every backward
         if static_rows:
@@ -199,10 +199,10 @@ class _NeuralDecode(torch.autograd.Function):
         d_feat, d_anchor, d_offset, d_scaling = [p_.view(sh) for p_, sh in zip(torch.split(flat, sizes), shapes)]
         gp = {nm: (None if prm[nm] is None else torch.empty_like(prm[nm])) for nm in PARAM_NAMES}
         ig = InGrads(ptr(d_anchor), ptr(d_feat), ptr(d_offset), ptr(d_scaling), Params(*[ptr(gp[nm]) for nm in PARAM_NAMES]))
-        scratch = torch.empty(L.gsd_backward_scratch_bytes(C.byref(cfg)), dtype=torch.uint8, device=dev)
+        work = scratch(L.gsd_backward_scratch_bytes(C.byref(cfg)), dev)
         # parameters are unchanged between forward and backward of one graph, so the forward's repacked weights are reused
-        check(L.gsd_backward(C.byref(cfg), C.byref(inp), C.byref(cp), ptr(nop), ptr(row_offset), n, C.byref(ogr), C.byref(ig),
-                             ptr(fwd_scratch), ptr(scratch), scratch.numel(), stream_ptr(dev)), "decode backward")
+        call("gsd_backward", dev, C.byref(cfg), C.byref(inp), C.byref(cp), nop, row_offset, n, C.byref(ogr), C.byref(ig), fwd_scratch, work, work.numel(),
+             what="decode backward")
         return (None, None, None, None, None, d_anchor, d_feat, d_offset, d_scaling, *[gp[nm] for nm in PARAM_NAMES])
 
 
@@ -311,6 +311,6 @@ def training_stats_(opacity_accum, anchor_demon, offset_gradient_accum, offset_d
         upd8 = upd.contiguous().view(torch.uint8) if upd.dtype == torch.bool else upd.to(torch.uint8).contiguous()
         vi = vis_idx.to(torch.int32).contiguous()
         dev = g.device
-        scratch = torch.empty(max(L.gsd_training_stats_scratch_bytes(Nv), 8), dtype=torch.uint8, device=dev)
-        check(L.gsd_training_stats(Nv, k, ptr(vi), ptr(no), ptr(sel8), ptr(upd8), ptr(g), int(g.shape[1]), ptr(opacity_accum), ptr(anchor_demon),
-                                   ptr(offset_gradient_accum), ptr(offset_denom), ptr(scratch), scratch.numel(), stream_ptr(dev)), "training_stats")
+        work = scratch(L.gsd_training_stats_scratch_bytes(Nv), dev)
+        call("gsd_training_stats", dev, Nv, k, vi, no, sel8, upd8, g, int(g.shape[1]), opacity_accum, anchor_demon, offset_gradient_accum, offset_denom,
+             work, work.numel())

@@ -16,7 +16,7 @@ import functools
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, scratch
 from ._rows import Args, Compute, Tensor, groups, install_
 from ._rows import _f32 as _rows_f32, moments as _moments
 
@@ -128,72 +128,71 @@ def clone_split_prune(params, moments, xyz_gradient_accum, denom, scaling_act, o
     if pgsr:
         a.accum_abs, a.denom_abs = stats["xyz_gradient_accum_abs"].data_ptr(), stats["denom_abs"].data_ptr()
     a.scaling, a.opacity, a.max_radii2D = scaling_act.data_ptr(), stats["opacity_act"].data_ptr(), stats["max_radii2D"].data_ptr()
-    with torch.cuda.device(dev):
-        nbytes = L.gsr_densify_plan_scratch_bytes(P, N)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        status = torch.empty(8, dtype=torch.int32, device=dev)
+    nbytes = L.gsr_densify_plan_scratch_bytes(P, N)
+    work = scratch(nbytes, dev)
+    status = torch.empty(8, dtype=torch.int32, device=dev)
 
-        def plan(masked=False):
-            m = torch.empty(3, P, dtype=torch.float32, device=dev) if masked else None
-            a.masked_out = m.data_ptr() if masked else None
-            check(L.gsr_densify_plan(C.byref(a), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)), "densify_plan")
-            a.masked_out = None
-            return status.tolist(), m                            # the host synchronisation
+    def plan(masked=False):
+        m = torch.empty(3, P, dtype=torch.float32, device=dev) if masked else None
+        a.masked_out = m.data_ptr() if masked else None
+        call("gsr_densify_plan", dev, C.byref(a), work, nbytes, status)
+        a.masked_out = None
+        return status.tolist(), m                            # the host synchronisation
 
-        c, _ = plan()
-        if pgsr and max_all_points is not None and P:
-            # pgsr_gaussian.py:69-86,111-117: a cap that binds replaces a threshold by a quantile of the masked gradients and a strict `>`
-            def cap(masked_row, pad, limited, n):
-                v = torch.cat((masked_row, torch.zeros(pad, dtype=torch.float32, device=dev))) if pad else masked_row
-                return float(torch.quantile(v, 1.0 - limited / float(n)))
-            if c[0] + P > max_all_points:
+    c, _ = plan()
+    if pgsr and max_all_points is not None and P:
+        # pgsr_gaussian.py:69-86,111-117: a cap that binds replaces a threshold by a quantile of the masked gradients and a strict `>`
+        def cap(masked_row, pad, limited, n):
+            v = torch.cat((masked_row, torch.zeros(pad, dtype=torch.float32, device=dev))) if pad else masked_row
+            return float(torch.quantile(v, 1.0 - limited / float(n)))
+        if c[0] + P > max_all_points:
+            _, m = plan(masked=True)
+            a.clone_cap = cap(m[0], 0, max_all_points - P, P); a.flags |= CLONE_CAP
+            c, _ = plan()
+        n = P + c[0]
+        if c[5] + n > max_all_points:
+            _, m = plan(masked=True)
+            a.split_cap = cap(m[1], c[0], max_all_points - n, n); a.flags |= SPLIT_CAP
+            c, _ = plan()
+        else:
+            limited = max_all_points - n - c[5]
+            if max_abs_split_points is not None:
+                limited = min(limited, max_abs_split_points)
+            if c[1] - c[5] > limited:
                 _, m = plan(masked=True)
-                a.clone_cap = cap(m[0], 0, max_all_points - P, P); a.flags |= CLONE_CAP
+                a.abs_cap = cap(m[2], c[0], limited, n); a.flags |= ABS_CAP
                 c, _ = plan()
-            n = P + c[0]
-            if c[5] + n > max_all_points:
-                _, m = plan(masked=True)
-                a.split_cap = cap(m[1], c[0], max_all_points - n, n); a.flags |= SPLIT_CAP
-                c, _ = plan()
-            else:
-                limited = max_all_points - n - c[5]
-                if max_abs_split_points is not None:
-                    limited = min(limited, max_abs_split_points)
-                if c[1] - c[5] > limited:
-                    _, m = plan(masked=True)
-                    a.abs_cap = cap(m[2], c[0], limited, n); a.flags |= ABS_CAP
-                    c, _ = plan()
-        n_clone, n_split, n_o, n_c, n_s = c[0], c[1], c[2], c[3], c[4]
-        rows = n_o + n_c + N * n_s
-        if noise_split is not None and noise_split.shape[0] != N * n_split:
-            raise RuntimeError(f"noise_split: expected {N * n_split} rows (N = {N} draws for each of {n_split} split Gaussians) but found {noise_split.shape[0]}")
-        if noise_clone is not None and noise_clone.shape[0] != n_clone:
-            raise RuntimeError(f"noise_clone: expected {n_clone} rows (one draw per cloned Gaussian) but found {noise_clone.shape[0]}")
-        if noise_split is None:
-            noise_split = torch.randn(N * n_split, 3, dtype=torch.float32, device=dev, generator=generator)
-        if pgsr and noise_clone is None:
-            noise_clone = torch.randn(n_clone, 3, dtype=torch.float32, device=dev, generator=generator)
-        if not pgsr:
-            noise_clone = None                                   # 3DGS / 2DGS clone in place
-        out_p, out_m = {}, {}
-        table = (Tensor * (3 * len(srcs)))()
-        k = 0
-        for name, (t, rb) in srcs.items():
-            o = torch.empty((rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-            out_p[name] = o
-            outs = [(t, o, 0)]
-            if name in moments:
-                mo = tuple(torch.empty_like(o) for _ in range(2))
-                out_m[name] = mo
-                outs += [(moments[name][0], mo[0], 1), (moments[name][1], mo[1], 1)]
-            if rb and rows and P:                                # a zero-width tensor (f_rest at degree 0) keeps its shape and copies nothing
-                for s, d, z in outs:
-                    table[k] = Tensor(s.data_ptr(), d.data_ptr(), rb, z, 0); k += 1
-        if rows:
-            cc = Compute(xyz.data_ptr(), srcs["rotation"][0].data_ptr(), out_p["xyz"].data_ptr(), out_p["scaling"].data_ptr(),
-                         noise_split.data_ptr() if noise_split.numel() else None, noise_clone.data_ptr() if noise_clone is not None and noise_clone.numel() else None)
-            counts = (C.c_uint32 * 8)(*c)
-            check(L.gsr_densify_emit(C.byref(a), ptr(scratch), nbytes, counts, k, table, C.byref(cc), stream_ptr(dev)), "densify_emit")
+    n_clone, n_split, n_o, n_c, n_s = c[0], c[1], c[2], c[3], c[4]
+    rows = n_o + n_c + N * n_s
+    if noise_split is not None and noise_split.shape[0] != N * n_split:
+        raise RuntimeError(f"noise_split: expected {N * n_split} rows (N = {N} draws for each of {n_split} split Gaussians) but found {noise_split.shape[0]}")
+    if noise_clone is not None and noise_clone.shape[0] != n_clone:
+        raise RuntimeError(f"noise_clone: expected {n_clone} rows (one draw per cloned Gaussian) but found {noise_clone.shape[0]}")
+    if noise_split is None:
+        noise_split = torch.randn(N * n_split, 3, dtype=torch.float32, device=dev, generator=generator)
+    if pgsr and noise_clone is None:
+        noise_clone = torch.randn(n_clone, 3, dtype=torch.float32, device=dev, generator=generator)
+    if not pgsr:
+        noise_clone = None                                   # 3DGS / 2DGS clone in place
+    out_p, out_m = {}, {}
+    table = (Tensor * (3 * len(srcs)))()
+    k = 0
+    for name, (t, rb) in srcs.items():
+        o = torch.empty((rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        out_p[name] = o
+        outs = [(t, o, 0)]
+        if name in moments:
+            mo = tuple(torch.empty_like(o) for _ in range(2))
+            out_m[name] = mo
+            outs += [(moments[name][0], mo[0], 1), (moments[name][1], mo[1], 1)]
+        if rb and rows and P:                                # a zero-width tensor (f_rest at degree 0) keeps its shape and copies nothing
+            for s, d, z in outs:
+                table[k] = Tensor(s.data_ptr(), d.data_ptr(), rb, z, 0); k += 1
+    if rows:
+        cc = Compute(xyz.data_ptr(), srcs["rotation"][0].data_ptr(), out_p["xyz"].data_ptr(), out_p["scaling"].data_ptr(),
+                     noise_split.data_ptr() if noise_split.numel() else None, noise_clone.data_ptr() if noise_clone is not None and noise_clone.numel() else None)
+        counts = (C.c_uint32 * 8)(*c)
+        call("gsr_densify_emit", dev, C.byref(a), work, nbytes, counts, k, table, C.byref(cc))
     return out_p, out_m, {"clones": n_clone, "splits": n_split, "pruned": P + n_clone + (N - 1) * n_split - rows, "rows": rows}
 
 

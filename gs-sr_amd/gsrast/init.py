@@ -22,28 +22,27 @@ import math
 import numpy as np
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, one_device, raise_status, scratch, status_text
 from ._rows import _f32
 
 ERR_NONFINITE, ERR_KEY_RANGE, ERR_RANK = 1, 2, 4
 MAX_LEVELS = 32
 
 
+STATUS = {
+    ERR_NONFINITE: "a non-finite value (NaN or infinity) in the input",
+    ERR_KEY_RANGE: "a voxel key outside int32: (point - init_pos) / cell exceeds 2^31",
+    ERR_RANK: "a rank beyond the number of elements",
+}
+
+
 def status_message(what, status):
     """The text of the status word of a gsr_init.hip entry point."""
-    parts = []
-    if status & ERR_NONFINITE:
-        parts.append("a non-finite value (NaN or infinity) in the input")
-    if status & ERR_KEY_RANGE:
-        parts.append("a voxel key outside int32: (point - init_pos) / cell exceeds 2^31")
-    if status & ERR_RANK:
-        parts.append("a rank beyond the number of elements")
-    return f"gsrast {what}: status {status}: " + "; ".join(parts or ["unknown bits"])
+    return status_text(what, status, STATUS)
 
 
 def _raise_on(what, status):
-    if status:
-        raise RuntimeError(status_message(what, int(status)))
+    raise_status(what, int(status), STATUS)
 
 
 def ranks(q, n):
@@ -65,8 +64,7 @@ def _cam_quantiles(points, cam_infos, dist_ratio):
     """-> (all_dist [2C], status [1] uint32-as-int32), nothing read."""
     pts = _f32(points, "points", (None, 3))
     cams = _f32(cam_infos, "cam_infos", (None, 4))
-    if cams.device != pts.device:
-        raise RuntimeError("cam_infos must be on the device of points")
+    one_device(("points", pts), ("cam_infos", cams))
     N, Cn = pts.shape[0], cams.shape[0]
     if N < 1 or Cn < 1:
         raise RuntimeError(f"camera_dist_quantiles: expected at least one point and one camera but found {N} and {Cn}")
@@ -75,10 +73,8 @@ def _cam_quantiles(points, cam_infos, dist_ratio):
     out = torch.empty(2 * Cn, dtype=torch.float32, device=pts.device)
     status = torch.empty(1, dtype=torch.int32, device=pts.device)
     nbytes = int(L.gsr_cam_dist_quantiles_scratch_bytes(N, Cn))
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=pts.device)
-    with torch.cuda.device(pts.device):
-        check(L.gsr_cam_dist_quantiles(ptr(pts), N, ptr(cams), Cn, lo, hi, w, ptr(out), ptr(scratch), nbytes, ptr(status), stream_ptr(pts.device)),
-              "cam_dist_quantiles")
+    work = scratch(nbytes, pts.device)
+    call("gsr_cam_dist_quantiles", pts.device, pts, N, cams, Cn, lo, hi, w, out, work, nbytes, status)
     return out, status
 
 
@@ -102,9 +98,8 @@ def _select(values, targets):
     out = torch.empty(len(targets), dtype=torch.float32, device=v.device)
     status = torch.empty(1, dtype=torch.int32, device=v.device)
     nbytes = int(L.gsr_select_lerp_scratch_bytes(n))
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        check(L.gsr_select_lerp(ptr(v), n, None, len(targets), lo, hi, w, ptr(out), ptr(scratch), nbytes, ptr(status), stream_ptr(v.device)), "select_lerp")
+    work = scratch(nbytes, v.device)
+    call("gsr_select_lerp", v.device, v, n, None, len(targets), lo, hi, w, out, work, nbytes, status)
     return out, status
 
 
@@ -200,18 +195,16 @@ def _voxel_unique(pts, init_pos, cells, what):
     L = lib()
     ip, cl = (C.c_double * 3)(*init_pos), (C.c_double * Ln)(*cells)
     nbytes = int(L.gsr_voxel_unique_scratch_bytes(N, Ln))
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=pts.device)
+    work = scratch(nbytes, pts.device)
     record = torch.empty(1 + Ln, dtype=torch.int32, device=pts.device)
-    with torch.cuda.device(pts.device):
-        check(L.gsr_voxel_unique_count(ptr(pts), N, Ln, ip, cl, mode, ptr(scratch), nbytes, ptr(record), stream_ptr(pts.device)), "voxel_unique_count")
-        host = record.tolist()                                                            # the one host read: status and every level's count
-        _raise_on(what, host[0] & 0xFFFFFFFF)
-        rec = (C.c_uint32 * (1 + Ln))(*[h & 0xFFFFFFFF for h in host])
-        U = sum(host[1:])
-        positions = torch.empty(U, 3, dtype=torch.float32, device=pts.device)
-        level = torch.empty(U, dtype=torch.int32, device=pts.device)
-        check(L.gsr_voxel_unique_emit(ptr(pts), N, Ln, ip, cl, mode, ptr(scratch), nbytes, rec, ptr(positions), ptr(level), stream_ptr(pts.device)),
-              "voxel_unique_emit")
+    call("gsr_voxel_unique_count", pts.device, pts, N, Ln, ip, cl, mode, work, nbytes, record)
+    host = record.tolist()                                                            # the one host read: status and every level's count
+    _raise_on(what, host[0] & 0xFFFFFFFF)
+    rec = (C.c_uint32 * (1 + Ln))(*[h & 0xFFFFFFFF for h in host])
+    U = sum(host[1:])
+    positions = torch.empty(U, 3, dtype=torch.float32, device=pts.device)
+    level = torch.empty(U, dtype=torch.int32, device=pts.device)
+    call("gsr_voxel_unique_emit", pts.device, pts, N, Ln, ip, cl, mode, work, nbytes, rec, positions, level)
     return positions, level, host[1:]
 
 

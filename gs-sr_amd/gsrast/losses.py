@@ -3,7 +3,7 @@ import threading
 
 import torch
 
-from . import lib, check, ptr, stream_ptr, dev_f32
+from . import lib, call, scratch, dev_f32
 
 
 # Zero-initialised scalars for kernels that accumulate a loss value with atomics: one torch.zeros(1024) serves 1024 calls (a fill kernel per
@@ -39,8 +39,7 @@ class _L1PlusLinear(torch.autograd.Function):
             raise RuntimeError("aux and waux must both be given and have the same number of elements")
         dcol = torch.empty_like(c)
         loss = zero_scalar(c.device)
-        check(lib().gsr_loss_l1_linear(c.numel(), ptr(c), ptr(g), ptr(dcol), a.numel() if a is not None else 0, ptr(a), ptr(w),
-                                       ptr(loss), stream_ptr(c.device)), "loss_l1_linear")
+        call("gsr_loss_l1_linear", c.device, c.numel(), c, g, dcol, a.numel() if a is not None else 0, a, w, loss)
         ctx.save_for_backward(dcol, w if w is not None else torch.empty(0, device=c.device))
         ctx.has_aux = a is not None
         ctx.root = bool(root)
@@ -74,8 +73,7 @@ class _ScalingProd(torch.autograd.Function):
             raise RuntimeError("scaling_prod_mean: count must be a device int32 tensor")
         grad = torch.empty_like(s)
         loss = zero_scalar(s.device)
-        check(lib().gsr_loss_scaling_prod(s.shape[0], int(cols), s.shape[1], ptr(s), ptr(count) if count is not None else None, float(lam), ptr(loss),
-                                          ptr(grad), stream_ptr(s.device)), "loss_scaling_prod")
+        call("gsr_loss_scaling_prod", s.device, s.shape[0], int(cols), s.shape[1], s, count, float(lam), loss, grad)
         ctx.save_for_backward(grad)
         ctx.unit = bool(unit_upstream)
         return loss
@@ -107,9 +105,8 @@ class _L1SSIM(torch.autograd.Function):
         L = lib()
         out = torch.empty(3, dtype=torch.float32, device=x.device)
         dimg = torch.empty_like(x)
-        scratch = torch.empty(L.gsr_loss_l1_ssim_scratch_bytes(Cc, H, W), dtype=torch.uint8, device=x.device)
-        check(L.gsr_loss_l1_ssim(Cc, H, W, ptr(x), ptr(y), float(lambda_dssim), ptr(out), ptr(dimg), ptr(scratch), scratch.numel(),
-                                 stream_ptr(x.device)), "loss_l1_ssim")
+        work = scratch(L.gsr_loss_l1_ssim_scratch_bytes(Cc, H, W), x.device)
+        call("gsr_loss_l1_ssim", x.device, Cc, H, W, x, y, float(lambda_dssim), out, dimg, work, work.numel())
         ctx.save_for_backward(dimg)
         parts = out[:2].detach()
         ctx.mark_non_differentiable(parts)
@@ -159,9 +156,9 @@ class _SurfelGeo(torch.autograd.Function):
         depth = torch.empty(1, H, W, dtype=torch.float32, device=dev) if want_maps else None
         nw = torch.empty(3, H, W, dtype=torch.float32, device=dev) if want_maps else None
         sn = torch.empty(3, H, W, dtype=torch.float32, device=dev) if want_maps else None
-        scratch = torch.empty(max(L.gsr_loss_surfel_geo_scratch_bytes(H, W), 8), dtype=torch.uint8, device=dev)
-        check(L.gsr_loss_surfel_geo(H, W, ptr(am), ptr(rm), ptr(nr), float(depth_ratio), float(lambda_normal), float(lambda_dist), ptr(out),
-                                    ptr(dL), ptr(depth), ptr(nw), ptr(sn), ptr(scratch), scratch.numel(), stream_ptr(dev)), "loss_surfel_geo")
+        work = scratch(L.gsr_loss_surfel_geo_scratch_bytes(H, W), dev)
+        call("gsr_loss_surfel_geo", dev, H, W, am, rm, nr, float(depth_ratio), float(lambda_normal), float(lambda_dist), out, dL, depth, nw, sn, work,
+             work.numel())
         ctx.save_for_backward(dL)
         parts = out[:2].detach()
         extras = [parts] + ([depth, nw, sn] if want_maps else [])
@@ -198,10 +195,9 @@ def _plane_geo_fwd(plane_depth, out_all_map, weight, ray_mat, lambda_normal, wan
     dA = torch.empty_like(am)                       # the kernel writes every pixel of the three normal channels;
     dA[3:].zero_()                                  # channels 3 (alpha, detached) and 4 (distance) get no gradient here
     dn = torch.empty(3, H, W, dtype=torch.float32, device=dev) if want_map else None
-    scratch = torch.empty(max(L.gsr_loss_surfel_geo_scratch_bytes(H, W), 8), dtype=torch.uint8, device=dev)
+    work = scratch(L.gsr_loss_surfel_geo_scratch_bytes(H, W), dev)
     alpha = am[3]
-    check(L.gsr_loss_plane_geo(H, W, ptr(d), ptr(alpha), ptr(am), ptr(w), ptr(rm), float(lambda_normal), ptr(out), ptr(dD), ptr(dA), ptr(dn),
-                               ptr(scratch), scratch.numel(), stream_ptr(dev)), "loss_plane_geo")
+    call("gsr_loss_plane_geo", dev, H, W, d, alpha, am, w, rm, float(lambda_normal), out, dD, dA, dn, work, work.numel())
     return out, dD, dA, dn
 
 
@@ -282,9 +278,8 @@ def sample_valid_pixels(d_mask, num_sample, generator=None, seed=None):
     m8 = m.contiguous() if m.dtype == torch.uint8 else m.to(torch.uint8).contiguous()
     L = lib()
     out = torch.empty(num_sample, dtype=torch.int32, device=m.device)
-    scratch = torch.empty(L.gsr_sample_mask_scratch_bytes(n), dtype=torch.uint8, device=m.device)
-    check(L.gsr_sample_mask(n, ptr(m8), int(num_sample), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(scratch), scratch.numel(), stream_ptr(m.device)),
-          "sample_mask")
+    work = scratch(L.gsr_sample_mask_scratch_bytes(n), m.device)
+    call("gsr_sample_mask", m.device, n, m8, int(num_sample), int(seed) & 0xFFFFFFFFFFFFFFFF, out, work, work.numel())
     return out
 
 
@@ -317,9 +312,8 @@ class _PlaneMultiview(torch.autograd.Function):
         dmask = torch.empty(H * W, dtype=torch.uint8, device=dev)
         stats = f(6)
         nmax = min(int(num_sample), H * W) if indices is None else int(indices.numel())
-        scratch = torch.empty(max(L.gsr_loss_plane_mv_scratch_bytes(W, H, nmax), 8), dtype=torch.uint8, device=dev)
-        check(L.gsr_loss_plane_mv_geo(C.byref(cfg), ptr(d), ptr(nd), ptr(noise), ptr(dmask), ptr(weight), ptr(stats), ptr(gD), ptr(gN), ptr(scratch),
-                                      scratch.numel(), stream_ptr(dev)), "loss_plane_mv_geo")
+        work = scratch(L.gsr_loss_plane_mv_scratch_bytes(W, H, nmax), dev)
+        call("gsr_loss_plane_mv_geo", dev, C.byref(cfg), d, nd, noise, dmask, weight, stats, gD, gN, work, work.numel())
         if indices is None:
             indices = sample_valid_pixels(dmask, num_sample, generator)
         idx = indices.to(device=dev, dtype=torch.int32).contiguous()
@@ -331,11 +325,11 @@ class _PlaneMultiview(torch.autograd.Function):
             gNm, gDs = gAM[0:3], gAM[3]
         ncc = f(max(idx.numel(), 1))
         cmask = torch.empty(max(idx.numel(), 1), dtype=torch.uint8, device=dev)
-        check(L.gsr_loss_plane_mv_ncc(C.byref(cfg), int(idx.numel()), ptr(idx), ptr(weight), ptr(nm), ptr(ds), ptr(g), ptr(ng), ptr(ncc), ptr(cmask),
-                                      ptr(stats[3:]), ptr(gNm), ptr(gDs), ptr(scratch), scratch.numel(), stream_ptr(dev)), "loss_plane_mv_ncc")
+        call("gsr_loss_plane_mv_ncc", dev, C.byref(cfg), int(idx.numel()), idx, weight, nm, ds, g, ng, ncc, cmask, stats[3:], gNm, gDs, work,
+             work.numel())
         # loss values lambda * mean on the device, one launch (the means' 1 / count and the lambdas reach the gradient maps in backward, one launch too)
         vals = f(2)
-        check(L.gsr_loss_plane_mv_values(ptr(stats), float(lambda_geo), float(lambda_ncc), ptr(vals), stream_ptr(dev)), "loss_plane_mv_values")
+        call("gsr_loss_plane_mv_values", dev, stats, float(lambda_geo), float(lambda_ncc), vals)
         geo, nccl = vals[0], vals[1]
         # single_view = (ray_mat, weight, lambda_normal): the single-view normal loss of the same render (plane_geo_loss) evaluated by THIS node, so that
         # its gradients to plane_depth / out_all_map leave backward already summed with the multi-view ones (plane_losses below)
@@ -366,7 +360,6 @@ class _PlaneMultiview(torch.autograd.Function):
         g_sv = rest[0] if ctx.has_sv else None
         s0, s1, s2, s3 = ctx.shapes
         lg, ln = ctx.lams
-        L = lib()
         dev = gD.device
         up = lambda g: None if g is None else g.reshape(1).to(torch.float32)      # a view for the float32 scalars autograd sends
         ug, un, us = up(g_geo), up(g_ncc), up(g_sv)   # a loss the caller did not use sends no gradient: its maps are not produced
@@ -374,10 +367,9 @@ class _PlaneMultiview(torch.autograd.Function):
         oD = torch.empty_like(gD) if (ug is not None or add) else None
         oN = torch.empty_like(gN) if ug is not None else None
         oA = torch.empty_like(gAM) if (un is not None or add) else None
-        check(L.gsr_loss_plane_mv_scale(gD.numel() if oD is not None else 0, gN.numel() if oN is not None else 0, gAM.numel() if oA is not None else 0,
-                                        ptr(gD) if ug is not None else None, ptr(gN), ptr(gAM) if un is not None else None, ptr(stats), lg, ln, ptr(ug), ptr(un),
-                                        ptr(svD) if add else None, ptr(svA) if add else None, ptr(us), 1 if add else 0,
-                                        ptr(oD), ptr(oN), ptr(oA), stream_ptr(dev)), "loss_plane_mv_scale")
+        call("gsr_loss_plane_mv_scale", dev, gD.numel() if oD is not None else 0, gN.numel() if oN is not None else 0, gAM.numel() if oA is not None else 0,
+             gD if ug is not None else None, gN, gAM if un is not None else None, stats, lg, ln, ug, un, svD if add else None, svA if add else None, us,
+             1 if add else 0, oD, oN, oA)
         gd = None if oD is None else oD.view(s0)
         gn = None if oN is None else oN.view(s1)
         if ctx.whole:                              # the whole (5,H,W) gradient of out_all_map

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, scratch
 from ._abi import gsr_mesh_filter as Filter, gsr_rows_tensor as RowsTensor
 
 DROP_UNREFERENCED, DROP_DEGENERATE = 1, 2             # include/gsrast.h GSR_MESH_DROP_*
@@ -39,7 +39,7 @@ def _scratch(T, V, dev):
     n = int(lib().gsr_mesh_post_scratch_bytes(T, V))
     if n == 0:
         raise RuntimeError(f"mesh: {T} triangles / {V} vertices: 3T must stay below 2^31 (the half-edges are indexed with 32 bits); filter the mesh in parts")
-    return torch.empty(n, dtype=torch.uint8, device=dev), n
+    return scratch(n, dev), n
 
 
 def _raise_status(status):
@@ -59,11 +59,9 @@ def cluster_connected_triangles(mesh, with_area=True):
     clusters = torch.empty(T, dtype=torch.int32, device=dev)
     counts = torch.empty(T, dtype=torch.int32, device=dev)
     area = torch.empty(T, dtype=torch.float64, device=dev) if with_area else None
-    scratch, nbytes = _scratch(T, 0, dev)
+    work, nbytes = _scratch(T, 0, dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().gsr_mesh_cluster_triangles(ptr(t), T, V, ptr(v) if with_area else None, ptr(clusters), ptr(counts), ptr(area), ptr(scratch), nbytes,
-                                               ptr(status), stream_ptr(dev)), "mesh_cluster_triangles")
+    call("gsr_mesh_cluster_triangles", dev, t, T, V, v if with_area else None, clusters, counts, area, work, nbytes, status)
     st, n = status.tolist()
     _raise_status(st)
     return clusters, counts[:n].clone(), (area[:n].clone() if with_area else None)
@@ -75,25 +73,23 @@ def _filter(mesh, remove_mask=None, cluster_to_keep=0, flags=0):
     v, c, t = _arrays(mesh)
     T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
     f = Filter(t.data_ptr() if T else None, None if remove_mask is None else remove_mask.data_ptr(), T, V, int(cluster_to_keep), FLOOR, int(flags), 0)
-    scratch, nbytes = _scratch(T, V, dev)
+    work, nbytes = _scratch(T, V, dev)
     record = torch.empty(8, dtype=torch.int32, device=dev)
     L = lib()
-    with torch.cuda.device(dev):
-        check(L.gsr_mesh_filter_count(C.byref(f), ptr(scratch), nbytes, ptr(record), stream_ptr(dev)), "mesh_filter_count")
-        rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back
-        if rec[0] & ERR_KEEP and not rec[0] & (ERR_INDEX | ERR_INTERNAL):
-            raise IndexError(f"index -{cluster_to_keep} is out of bounds for axis 0 with size {rec[1]}")      # numpy's words for n[-cluster_to_keep]
-        _raise_status(rec[0])
-        n_v, n_t = rec[3], rec[4]
-        tris = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
-        rows, n_rows = None, 0
-        if flags & DROP_UNREFERENCED:
-            nv, nc = torch.empty((n_v, 3), dtype=torch.float32, device=dev), torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-            rows, n_rows = (RowsTensor * 2)(RowsTensor(v.data_ptr(), nv.data_ptr(), None, 12, 0), RowsTensor(c.data_ptr(), nc.data_ptr(), None, 12, 0)), 2
-        else:
-            nv, nc = v, c
-        check(L.gsr_mesh_filter_emit(C.byref(f), ptr(scratch), nbytes, (C.c_uint32 * 8)(*rec), n_rows, rows, ptr(tris) if n_t else None, stream_ptr(dev)),
-              "mesh_filter_emit")
+    call("gsr_mesh_filter_count", dev, C.byref(f), work, nbytes, record)
+    rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back
+    if rec[0] & ERR_KEEP and not rec[0] & (ERR_INDEX | ERR_INTERNAL):
+        raise IndexError(f"index -{cluster_to_keep} is out of bounds for axis 0 with size {rec[1]}")      # numpy's words for n[-cluster_to_keep]
+    _raise_status(rec[0])
+    n_v, n_t = rec[3], rec[4]
+    tris = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+    rows, n_rows = None, 0
+    if flags & DROP_UNREFERENCED:
+        nv, nc = torch.empty((n_v, 3), dtype=torch.float32, device=dev), torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        rows, n_rows = (RowsTensor * 2)(RowsTensor(v.data_ptr(), nv.data_ptr(), None, 12, 0), RowsTensor(c.data_ptr(), nc.data_ptr(), None, 12, 0)), 2
+    else:
+        nv, nc = v, c
+    call("gsr_mesh_filter_emit", dev, C.byref(f), work, nbytes, (C.c_uint32 * 8)(*rec), n_rows, rows, tris if n_t else None)
     return nv, nc, tris, rec
 
 

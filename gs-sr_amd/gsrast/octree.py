@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from . import EWA, LodCfg, check, dev_f32, lib, make_cfg, ptr, stream_ptr
+from . import EWA, LodCfg, call, dev_f32, make_cfg, one_device
 
 MODES = {"floor": 0, "round": 1, "ceil": 2, "progressive": 3}
 
@@ -36,9 +36,9 @@ def octree_visible(raster_settings, anchor, level, scaling, rotation, voxel_size
         if Na:
             keep = []
             cfg = make_cfg(EWA, Na, raster_settings, 0, 0, False, keep)
+            one_device(("anchor", a), *zip(("bg", "viewmatrix", "projmatrix", "campos"), keep))
             lod = LodCfg(float(voxel_size), float(fork), float(standard_dist), float(resolution_scale), int(coarse_index), MODES[dist2level])
-            check(lib().gsr_octree_visible(C.byref(cfg), C.byref(lod), ptr(a), ptr(lv), ptr(ex), ptr(sc), int(sc.shape[1]), ptr(ro), ptr(amask),
-                                           ptr(radii), ptr(prog), ptr(trans), stream_ptr(dev)), "octree_visible")
+            call("gsr_octree_visible", dev, C.byref(cfg), C.byref(lod), a, lv, ex, sc, int(sc.shape[1]), ro, amask, radii, prog, trans)
         return {"anchor_mask": amask.view(torch.bool), "visible_mask": radii > 0, "radii": radii, "prog_ratio": prog,
                 "transition_mask": None if trans is None else trans.view(torch.bool)}
 
@@ -55,10 +55,8 @@ def weed_out(positions, levels_of, cam_infos, standard_dist, fork, levels, dist2
             raise RuntimeError(f"levels_of: expected a tensor of {U} entries on the device of positions")
         lv = levels_of.reshape(-1).to(torch.int32).contiguous()
         w, cams = make_weed(cam_infos, standard_dist, fork, levels, dist2level, visible_threshold)
-        if cams.device != pos.device:
-            raise RuntimeError("cam_infos must be on the device of positions")
+        one_device(("positions", pos), ("cam_infos", cams))
         count = torch.empty(U, dtype=torch.int32, device=pos.device)
         keep = torch.empty(U, dtype=torch.uint8, device=pos.device)
-        with torch.cuda.device(pos.device):
-            check(lib().gsr_octree_weed_out(ptr(pos), ptr(lv), U, C.byref(w), ptr(count), ptr(keep), stream_ptr(pos.device)), "octree_weed_out")
+        call("gsr_octree_weed_out", pos.device, pos, lv, U, C.byref(w), count, keep)
         return count, keep.view(torch.bool)

@@ -25,7 +25,7 @@ import math
 import torch
 from torch.optim.adam import adam as _torch_adam
 
-from . import check, lib, stream_ptr
+from . import call
 from ._abi import gsr_adam_tensor as _AdamTensor
 
 
@@ -96,7 +96,6 @@ class Adam(torch.optim.Adam):
             with torch.enable_grad():
                 loss = closure()
         shadows = self.__dict__.get("_gsr_shadows", {})
-        L = lib()
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         captured = []                              # capture: (param, group) in table order, for prepare_replay
         steps = self.__dict__.setdefault("_gsr_step_views", {})
@@ -170,24 +169,23 @@ class Adam(torch.optim.Adam):
                                                                        # graphs over one optimizer (one per image size, say) each replay their own
         for dev, entries in batch.items():
             table = (_AdamTensor * len(entries))(*entries)
-            with torch.cuda.device(dev):
-                if capturing:
-                    # The buffer the recorded launch reads its per-step scalars from must NOT come from the graph's private pool: a block of that
-                    # pool may have held a temporary earlier in the recorded iteration, whose recorded writes would then overwrite, on every
-                    # replay, what prepare_replay() copied in beforehand (measured: step_size read back as 0).  It is created by the eager
-                    # step() calls that precede every capture (torch.cuda.graph needs warm-up iterations anyway).
-                    # Every capture takes the spare buffer for itself (its recorded launch reads table position i of it for the i-th captured tensor);
-                    # the next eager step() provides a new spare.
-                    hyper = self.__dict__.get("_gsr_hyper", {}).pop(dev, None)
-                    if hyper is None or hyper.shape[0] < len(entries):
-                        raise RuntimeError("gsrast.optim.Adam: run at least one eager step() before recording each step() into a graph")
-                    graphs.append([captured, hyper, [], 0])
-                    check(L.gsr_adam_step_multi_dev(len(entries), table, hyper.data_ptr(), stream_ptr(dev)), "adam_step_multi_dev")
-                else:
-                    hy = self.__dict__.setdefault("_gsr_hyper", {})
-                    if dev not in hy or hy[dev].shape[0] < len(entries):
-                        hy[dev] = torch.zeros(len(entries) + 8, 2, dtype=torch.float32, device=dev)
-                    check(L.gsr_adam_step_multi(len(entries), table, stream_ptr(dev)), "adam_step_multi")
+            if capturing:
+                # The buffer the recorded launch reads its per-step scalars from must NOT come from the graph's private pool: a block of that
+                # pool may have held a temporary earlier in the recorded iteration, whose recorded writes would then overwrite, on every
+                # replay, what prepare_replay() copied in beforehand (measured: step_size read back as 0).  It is created by the eager
+                # step() calls that precede every capture (torch.cuda.graph needs warm-up iterations anyway).
+                # Every capture takes the spare buffer for itself (its recorded launch reads table position i of it for the i-th captured tensor);
+                # the next eager step() provides a new spare.
+                hyper = self.__dict__.get("_gsr_hyper", {}).pop(dev, None)
+                if hyper is None or hyper.shape[0] < len(entries):
+                    raise RuntimeError("gsrast.optim.Adam: run at least one eager step() before recording each step() into a graph")
+                graphs.append([captured, hyper, [], 0])
+                call("gsr_adam_step_multi_dev", dev, len(entries), table, hyper)
+            else:
+                hy = self.__dict__.setdefault("_gsr_hyper", {})
+                if dev not in hy or hy[dev].shape[0] < len(entries):
+                    hy[dev] = torch.zeros(len(entries) + 8, 2, dtype=torch.float32, device=dev)
+                call("gsr_adam_step_multi", dev, len(entries), table)
         if capturing:
             return loss
         for group, ps in rest:                     # uncovered parameters: exactly torch's update (its functional form on a copy of the group

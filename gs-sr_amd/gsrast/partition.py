@@ -24,7 +24,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, raise_status, scratch, status_text, typed_tensor as _tensor
 
 ERR_FEW, ERR_NONFINITE, ERR_ZERO_Z, ERR_ABSENT, ERR_TABLE, ERR_OFFSETS, ERR_COUNT = 1, 2, 4, 8, 16, 32, 64
 MAX_TILES = 1024                                          # GSR_PART_MAX_TILES
@@ -32,38 +32,20 @@ BLOCK = 256                                               # GSR_PART_BLOCK: poin
 PINHOLE_ASSERT = "Colmap camera model not handled: only undistorted datasets (PINHOLE or SIMPLE_PINHOLE cameras) supported!"
 
 
+STATUS = {
+    ERR_FEW: "a tile has fewer than four points in its box, or no point's neighbour distance lies inside mean +- 3 std (the reference fails on an empty min())",
+    ERR_NONFINITE: "a non-finite value: a box bound, a point coordinate (as float32), a 3-sigma threshold or a term of a projection is NaN or infinite",
+    ERR_ZERO_Z: "a box corner has camera-space z exactly 0 (the reference gets a Qhull error)",
+    ERR_ABSENT: "a point id that an image of a tile observes is absent from the point table (the reference's KeyError)",
+    ERR_TABLE: "point_ids does not ascend strictly",
+    ERR_OFFSETS: "obs_offsets does not ascend from 0 to len(obs_ids)",
+    ERR_COUNT: "counts does not hold the number of bits of mask",
+}
+
+
 def status_message(op, status):
     """The text of a status word of the scene partition."""
-    parts = []
-    if status & ERR_FEW:
-        parts.append("a tile has fewer than four points in its box, or no point's neighbour distance lies inside mean +- 3 std (the reference fails on an empty min())")
-    if status & ERR_NONFINITE:
-        parts.append("a non-finite value: a box bound, a point coordinate (as float32), a 3-sigma threshold or a term of a projection is NaN or infinite")
-    if status & ERR_ZERO_Z:
-        parts.append("a box corner has camera-space z exactly 0 (the reference gets a Qhull error)")
-    if status & ERR_ABSENT:
-        parts.append("a point id that an image of a tile observes is absent from the point table (the reference's KeyError)")
-    if status & ERR_TABLE:
-        parts.append("point_ids does not ascend strictly")
-    if status & ERR_OFFSETS:
-        parts.append("obs_offsets does not ascend from 0 to len(obs_ids)")
-    if status & ERR_COUNT:
-        parts.append("counts does not hold the number of bits of mask")
-    return f"gsrast {op}: status {status}: " + "; ".join(parts or ["unknown bits"])
-
-
-def _tensor(t, name, dtype, shape, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{name}: expected {dtype} but found {t.dtype}")
-    if t.dim() != len(shape) or any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
-        raise RuntimeError(f"{name}: expected shape {[s if s is not None else '*' for s in shape]} but found {list(t.shape)}")
-    if device is not None and t.device != device:
-        raise RuntimeError(f"{name} must be on the device of {device}")
-    return t.detach().contiguous()
+    return status_text(op, status, STATUS)
 
 
 def _tiles(T, op):
@@ -73,9 +55,7 @@ def _tiles(T, op):
 
 
 def _raise(op, status):
-    st = int(status.item()) & 0xFFFFFFFF                  # the host read
-    if st:
-        raise RuntimeError(status_message(op, st))
+    raise_status(op, int(status.item()) & 0xFFFFFFFF, STATUS)      # the host read
 
 
 # ---------------------------------------------------------------------------------------------------------------- tensor level
@@ -96,9 +76,8 @@ def point_tiles(xy, boxes):
     mask = torch.empty(N, W, dtype=torch.int32, device=dev)
     counts = torch.empty(T, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().gsr_partition_boxes(ptr(xy) if N else None, N, xy.shape[1], ptr(bx), T, ptr(mask) if N else None, ptr(counts), ptr(status), stream_ptr(dev)), op)
-        _raise(op, status)
+    call("gsr_partition_boxes", dev, xy if N else None, N, xy.shape[1], bx, T, mask if N else None, counts, status, what=op)
+    _raise(op, status)
     return mask, counts
 
 
@@ -121,17 +100,15 @@ def tile_z_range(xyz, mask, counts):
     zrange = torch.zeros(T, 2, dtype=torch.float32, device=dev)
     stats = torch.zeros(T, 2, dtype=torch.float64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        host = [int(c) & 0xFFFFFFFF for c in cnt.cpu().tolist()]      # host read 1
-        n_max = max(host)
-        if n_max > N:
-            raise RuntimeError(status_message(op, ERR_COUNT))
-        nbytes = int(L.gsr_partition_zrange_scratch_bytes(N, n_max))
-        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        for t, n in enumerate(host):
-            check(L.gsr_partition_zrange(ptr(xyz) if N else None, N, ptr(mask) if N else None, T, t, n, n_max, ptr(zrange), ptr(stats), ptr(scratch), nbytes,
-                                         ptr(status), stream_ptr(dev)), op)
-        _raise(op, status)                                # host read 2
+    host = [int(c) & 0xFFFFFFFF for c in cnt.cpu().tolist()]      # host read 1
+    n_max = max(host)
+    if n_max > N:
+        raise RuntimeError(status_message(op, ERR_COUNT))
+    nbytes = int(L.gsr_partition_zrange_scratch_bytes(N, n_max))
+    work = scratch(nbytes, dev)
+    for t, n in enumerate(host):
+        call("gsr_partition_zrange", dev, xyz if N else None, N, mask if N else None, T, t, n, n_max, zrange, stats, work, nbytes, status, what=op)
+    _raise(op, status)                                # host read 2
     return zrange, stats
 
 
@@ -166,10 +143,8 @@ def visibility(boxes, zrange, w2c, centers, intr, member, threshold):
     md = torch.empty(T, dtype=torch.float64, device=dev)
     add = torch.empty(T, Cn, dtype=torch.uint8, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().gsr_partition_visibility(ptr(bx), ptr(zr), T, ptr(E), ptr(cen), ptr(K), Cn, ptr(mem), threshold, ptr(ratio), ptr(dist), ptr(md), ptr(add),
-                                             ptr(status), stream_ptr(dev)), op)
-        _raise(op, status)
+    call("gsr_partition_visibility", dev, bx, zr, T, E, cen, K, Cn, mem, threshold, ratio, dist, md, add, status, what=op)
+    _raise(op, status)
     return ratio, dist, md, add
 
 
@@ -206,19 +181,16 @@ def coverage(obs_offsets, obs_ids, image_mask, point_ids, num_tiles):
     L = lib()
     pmask = torch.empty(Np, W, dtype=torch.int32, device=dev)
     rec = torch.empty(T + 1, dtype=torch.int32, device=dev)      # counts, then the status word
-    with torch.cuda.device(dev):
-        check(L.gsr_partition_coverage_mask(ptr(off), ptr(ids) if M else None, M, ptr(im), Cn, ptr(pid) if Np else None, Np, T, ptr(pmask) if Np else None, ptr(rec),
-                                            ptr(rec[T:]), stream_ptr(dev)), op)
-        host = [int(v) & 0xFFFFFFFF for v in rec.cpu().tolist()]      # the one host read
-        if host[T]:
-            raise RuntimeError(status_message(op, host[T]))
-        offsets = np.zeros(T + 1, np.int64)
-        np.cumsum(host[:T], out=offsets[1:])
-        rows = torch.empty(int(offsets[T]), dtype=torch.int64, device=dev)
-        nbytes = int(L.gsr_partition_coverage_rows_scratch_bytes(Np))
-        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        check(L.gsr_partition_coverage_rows(ptr(pmask) if Np else None, Np, T, offsets.ctypes.data_as(C.POINTER(C.c_int64)), ptr(rows) if offsets[T] else None,
-                                            ptr(scratch), nbytes, stream_ptr(dev)), op)
+    call("gsr_partition_coverage_mask", dev, off, ids if M else None, M, im, Cn, pid if Np else None, Np, T, pmask if Np else None, rec, rec[T:], what=op)
+    host = [int(v) & 0xFFFFFFFF for v in rec.cpu().tolist()]      # the one host read
+    raise_status(op, host[T], STATUS)
+    offsets = np.zeros(T + 1, np.int64)
+    np.cumsum(host[:T], out=offsets[1:])
+    rows = torch.empty(int(offsets[T]), dtype=torch.int64, device=dev)
+    nbytes = int(L.gsr_partition_coverage_rows_scratch_bytes(Np))
+    work = scratch(nbytes, dev)
+    call("gsr_partition_coverage_rows", dev, pmask if Np else None, Np, T, offsets.ctypes.data_as(C.POINTER(C.c_int64)), rows if offsets[T] else None,
+         work, nbytes, what=op)
     return torch.from_numpy(offsets), rows
 
 

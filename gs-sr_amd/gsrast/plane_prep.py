@@ -4,7 +4,7 @@ Replaces, inside `PGSRScene.render()` (gssr/scene/pgsr_scene.py:297-304, with ge
 (quaternion_to_matrix, min, gather, masked negate, two matmuls, abs ...) and their ~40 autograd nodes by one streaming kernel each way."""
 import torch
 
-from . import check, dev_f32, lib, ptr, stream_ptr
+from . import call, dev_f32
 
 
 class _PlaneAllMap(torch.autograd.Function):
@@ -19,7 +19,7 @@ class _PlaneAllMap(torch.autograd.Function):
         if q.shape != (P, 4) or s.dim() != 2 or s.shape[0] != P or s.shape[1] < 3 or V.numel() != 16 or cp.numel() != 3:
             raise RuntimeError("plane_input_all_map: means3D (P,3), rotations (P,4), scales (P,>=3), viewmatrix (4,4), campos (3,) expected")
         out = torch.empty(P, 5, dtype=torch.float32, device=x.device)
-        check(lib().gsr_plane_allmap(P, ptr(x), ptr(q), ptr(s), int(s.shape[1]), ptr(V), ptr(cp), ptr(out), stream_ptr(x.device)), "plane_allmap")
+        call("gsr_plane_allmap", x.device, P, x, q, s, int(s.shape[1]), V, cp, out)
         ctx.save_for_backward(x, q, s, V, cp)
         return out
 
@@ -30,8 +30,7 @@ class _PlaneAllMap(torch.autograd.Function):
         P = x.shape[0]
         dx = torch.empty_like(x)
         dq = torch.empty_like(q)
-        check(lib().gsr_plane_allmap_backward(P, ptr(x), ptr(q), ptr(s), int(s.shape[1]), ptr(V), ptr(cp), ptr(g), ptr(dx), ptr(dq),
-                                              stream_ptr(x.device)), "plane_allmap_backward")
+        call("gsr_plane_allmap_backward", x.device, P, x, q, s, int(s.shape[1]), V, cp, g, dx, dq)
         return dx, dq, None, None, None
 
 

@@ -1,4 +1,4 @@
-"""Shared autograd bridge for the three rasterizer variants (the role of _RasterizeGaussians in
+"""The autograd bridge of the three rasterizer variants, one torch.autograd.Function for all of them (the role of _RasterizeGaussians in
 diff_gaussian_rasterization/__init__.py:44-155, diff_surfel_rasterization/__init__.py:44-156,
 diff_plane_rasterization/__init__.py:48-171) on top of the C ABI of libgsrast_hip.so.
 
@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-from . import (EWA, SURFEL, PLANE, Cfg, Inputs, Outputs, OutGrads, InGrads, lib, check, stream_ptr, dev_f32, ptr,
+from . import (EWA, SURFEL, PLANE, Inputs, Outputs, OutGrads, InGrads, lib, call, scratch, one_device, dev_f32, ptr,
                make_cfg)
 
 
@@ -29,10 +29,6 @@ _R_HINT = {}
 _R_OVERFLOWS = {}     # key -> [consecutive overflows, calls left on the exact path]
 _HINT_LOCK = threading.Lock()
 _SPECULATIVE = True           # (tests flip it to walk the exact stage1 -> sync -> stage2 path; it was the environment switch GSR_SPECULATIVE until round 6)
-
-
-def _bytes(n, device):
-    return torch.empty((max(int(n), 1),), dtype=torch.uint8, device=device)
 
 
 # ---- forward without any host synchronisation (gsr_forward_async): the form a HIP graph can record.  Selected inside `static_capacity(...)`
@@ -139,6 +135,8 @@ def _prepare(variant, means3D, sh, colors_precomp, opacities, scales, rotations,
     render_geo = bool(getattr(settings, "render_geo", False)) and t["all_map"] is not None
     cfg = make_cfg(variant, P, settings, settings.sh_degree, M, render_geo, keep)
     inp = Inputs(*[ptr(t[n]) for n, _ in Inputs._fields_])
+    one_device(*zip(("means3D", "sh", "colors", "opacity", "scales", "rotations", "cov3D_precomp", "all_map"), t.values()),
+               *zip(("bg", "viewmatrix", "projmatrix", "campos"), keep))
     keep.extend(v for v in t.values() if v is not None)
     return cfg, inp, keep, P, M
 
@@ -168,11 +166,10 @@ def forward(variant, means3D, sh, colors_precomp, opacities, scales, rotations, 
         geo = bool(cfg.render_geo) and not empty_call
         outs["all_map"] = (torch.empty if geo else torch.zeros)((5, H, W), **f32)
         outs["plane_depth"] = (torch.empty if geo else torch.zeros)((1, H, W), **f32)
-    geom = _bytes(L.gsr_geom_bytes(variant, P), dev)
-    img = _bytes(L.gsr_img_bytes(variant, W, H), dev)
+    geom = scratch(L.gsr_geom_bytes(variant, P), dev)
+    img = scratch(L.gsr_img_bytes(variant, W, H), dev)
     if empty_call:
-        return 0, outs, radii, geom, _bytes(0, dev), img
-    s = stream_ptr(dev)
+        return 0, outs, radii, geom, scratch(0, dev), img
     R = C.c_uint32(0)
     o = Outputs(ptr(outs["color"]), ptr(outs.get("others")), ptr(outs.get("observe")), ptr(outs.get("all_map")),
                 ptr(outs.get("plane_depth")))
@@ -199,36 +196,34 @@ def forward(variant, means3D, sh, colors_precomp, opacities, scales, rotations, 
             if h is None:
                 raise RuntimeError("gsrast: a sync-free forward needs a capacity: pass static_capacity(cap) or run the call once eagerly first")
             acap = int(h * 1.25) + 16384
-        binning = _bytes(L.gsr_binning_bytes(variant, int(acap), W, H), dev)
+        binning = scratch(L.gsr_binning_bytes(variant, int(acap), W, H), dev)
         status = _status_row(dev) if capturing else torch.zeros((3,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.gsr_forward_async(C.byref(cfg), C.byref(inp), ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img),
-                                      img.numel(), ptr(radii), C.byref(o), ptr(status), s), "forward_async")
+        call("gsr_forward_async", dev, C.byref(cfg), C.byref(inp), geom, geom.numel(), binning, binning.numel(), img, img.numel(), radii,
+             C.byref(o), status)
         cap = int(L.gsr_binning_capacity(variant, binning.numel(), W, H))
         _ASYNC_STATUS.append((status, cap))
         return cap, outs, radii, geom, binning, img
-    with torch.cuda.device(dev):
-        if hint is not None:
-            # steady state: one call, no GPU idle gap at the sync (arena sized from the previous call + 25 % head-room)
-            binning = _bytes(L.gsr_binning_bytes(variant, int(hint * 1.25) + 16384, W, H), dev)
-            ovf = C.c_int32(0)
-            check(L.gsr_forward(C.byref(cfg), C.byref(inp), ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img),
-                                img.numel(), ptr(radii), C.byref(o), C.byref(R), C.byref(ovf), s), "forward")
-            if ovf.value:
-                overflowed = True
-                binning = _bytes(L.gsr_binning_bytes(variant, R.value, W, H), dev)
-                if "observe" in outs:
-                    outs["observe"].zero_()
-                check(L.gsr_forward_stage2(C.byref(cfg), C.byref(inp), ptr(geom), geom.numel(), ptr(binning), binning.numel(),
-                                           ptr(img), img.numel(), R.value, C.byref(o), s), "forward")
-        else:
-            # the depth order stage 1 decided travels back with num_rendered and into stage 2, which is then a pure enqueue (ABI 7; the ABI <= 6 stage 2
-            # read the record back from the geom arena: a stream drain per two-stage forward)
-            order = C.c_uint32(0)
-            check(L.gsr_forward_stage1_ex(C.byref(cfg), C.byref(inp), ptr(geom), geom.numel(), ptr(radii), C.byref(R), C.byref(order), s), "forward")
-            binning = _bytes(L.gsr_binning_bytes(variant, R.value, W, H), dev)
-            check(L.gsr_forward_stage2_ex(C.byref(cfg), C.byref(inp), ptr(geom), geom.numel(), ptr(binning), binning.numel(),
-                                          ptr(img), img.numel(), R.value, order.value, C.byref(o), s), "forward")
+    if hint is not None:
+        # steady state: one call, no GPU idle gap at the sync (arena sized from the previous call + 25 % head-room)
+        binning = scratch(L.gsr_binning_bytes(variant, int(hint * 1.25) + 16384, W, H), dev)
+        ovf = C.c_int32(0)
+        call("gsr_forward", dev, C.byref(cfg), C.byref(inp), geom, geom.numel(), binning, binning.numel(), img, img.numel(), radii, C.byref(o),
+             C.byref(R), C.byref(ovf))
+        if ovf.value:
+            overflowed = True
+            binning = scratch(L.gsr_binning_bytes(variant, R.value, W, H), dev)
+            if "observe" in outs:
+                outs["observe"].zero_()
+            call("gsr_forward_stage2", dev, C.byref(cfg), C.byref(inp), geom, geom.numel(), binning, binning.numel(), img, img.numel(), R.value,
+                 C.byref(o), what="forward")
+    else:
+        # the depth order stage 1 decided travels back with num_rendered and into stage 2, which is then a pure enqueue (ABI 7; the ABI <= 6 stage 2
+        # read the record back from the geom arena: a stream drain per two-stage forward)
+        order = C.c_uint32(0)
+        call("gsr_forward_stage1_ex", dev, C.byref(cfg), C.byref(inp), geom, geom.numel(), radii, C.byref(R), C.byref(order), what="forward")
+        binning = scratch(L.gsr_binning_bytes(variant, R.value, W, H), dev)
+        call("gsr_forward_stage2_ex", dev, C.byref(cfg), C.byref(inp), geom, geom.numel(), binning, binning.numel(), img, img.numel(), R.value,
+             order.value, C.byref(o), what="forward")
     with _HINT_LOCK:
         prev = _R_HINT.get(key)
         _R_HINT[key] = int(R.value) if (prev is None or overflowed) else max(int(R.value), int(0.9 * prev))
@@ -267,24 +262,21 @@ def backward(variant, num_rendered, settings, radii, means3D, sh, colors_precomp
         return dev_f32(t, name) if t is not None else None
     og_t = [gd(grad_color, "dL_dout_color"), gd(grad_others, "dL_dout_others"), gd(grad_all_map, "dL_dout_all_map"),
             gd(grad_plane_depth, "dL_dout_plane_depth"), gd(all_map_pixels, "all_map_pixels")]
+    one_device(("means3D", means3D), *zip(("dL_dout_color", "dL_dout_others", "dL_dout_all_map", "dL_dout_plane_depth", "all_map_pixels"), og_t))
     og = OutGrads(*[ptr(t) for t in og_t])
     ig = InGrads(ptr(g["dL_dmeans3D"]), ptr(g["dL_dmeans2D"]), ptr(g.get("dL_dmeans2D_abs")), ptr(g["dL_dcolors"]),
                  ptr(g["dL_dopacity"]), ptr(g["dL_dcov3D"]), ptr(g["dL_dsh"]) if M > 0 else None, ptr(g["dL_dscales"]),
                  ptr(g["dL_drotations"]), ptr(g.get("dL_dall_map")))
     radii_c = radii.contiguous()
     if _ACC_REUSE:
-        akey, scratch = _acc_scratch(L, variant, P, dev)
-        with torch.cuda.device(dev):
-            check(L.gsr_backward_ex(C.byref(cfg), C.byref(inp), ptr(radii_c), ptr(geom), geom.numel(), ptr(binning),
-                                    binning.numel(), ptr(img), img.numel(), int(num_rendered), ptr(scratch), scratch.numel(),
-                                    C.byref(og), C.byref(ig), 3, stream_ptr(dev)), "backward")      # 3 = SCRATCH_IS_ZERO | LEAVE_ZERO
-        _acc_release(akey, scratch)             # only after a successful enqueue: a failed call may have left it dirty
+        akey, acc = _acc_scratch(L, variant, P, dev)
+        call("gsr_backward_ex", dev, C.byref(cfg), C.byref(inp), radii_c, geom, geom.numel(), binning, binning.numel(), img, img.numel(),
+             int(num_rendered), acc, acc.numel(), C.byref(og), C.byref(ig), 3, what="backward")      # 3 = SCRATCH_IS_ZERO | LEAVE_ZERO
+        _acc_release(akey, acc)                 # only after a successful enqueue: a failed call may have left it dirty
     else:
-        scratch = _bytes(L.gsr_backward_scratch_bytes(variant, P), dev)
-        with torch.cuda.device(dev):
-            check(L.gsr_backward(C.byref(cfg), C.byref(inp), ptr(radii_c), ptr(geom), geom.numel(), ptr(binning),
-                                 binning.numel(), ptr(img), img.numel(), int(num_rendered), ptr(scratch), scratch.numel(),
-                                 C.byref(og), C.byref(ig), stream_ptr(dev)), "backward")
+        acc = scratch(L.gsr_backward_scratch_bytes(variant, P), dev)
+        call("gsr_backward", dev, C.byref(cfg), C.byref(inp), radii_c, geom, geom.numel(), binning, binning.numel(), img, img.numel(),
+             int(num_rendered), acc, acc.numel(), C.byref(og), C.byref(ig))
     if sh is None or sh.numel() == 0 or M == 0:
         g["dL_dsh"] = torch.zeros((P, M, 3), **f32)
     return g
@@ -293,6 +285,75 @@ def backward(variant, num_rendered, settings, radii, means3D, sh, colors_precomp
 def debug_read(variant, field, settings, P, M, num_rendered, geom, binning, img, out):
     keep = []
     cfg = make_cfg(variant, P, settings, settings.sh_degree, M, False, keep)
-    check(lib().gsr_debug_read(C.byref(cfg), field, ptr(geom), ptr(binning), binning.numel(), ptr(img), int(num_rendered),
-                               ptr(out), stream_ptr(out.device)), "debug_read")
+    call("gsr_debug_read", out.device, C.byref(cfg), field, geom, binning, binning.numel(), img, int(num_rendered), out)
     return out
+
+
+def _snapshot(debug, args, file, message, fn):
+    """fn(), and with `debug` a host copy of `args` written to `file` when it raises (the reference's debug mode)."""
+    if not debug:
+        return fn()
+    cpu_args = cpu_deep_copy_tuple(args)       # copy them before they can be corrupted
+    try:
+        return fn()
+    except Exception as ex:
+        torch.save(cpu_args, file)
+        print(message)
+        raise ex
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    """The autograd node of the three drop-in packages.  EWA and SURFEL pass None for means2D_abs and all_map; gradients come back in the
+    argument order below, which holds each package's own order."""
+
+    @staticmethod
+    def forward(ctx, variant, means3D, means2D, means2D_abs, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map, raster_settings):
+        args = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map, raster_settings)
+        num_rendered, outs, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot(
+            raster_settings.debug, args, "snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.",
+            lambda: forward(variant, *args))
+        ctx.variant, ctx.raster_settings, ctx.num_rendered = variant, raster_settings, num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer, imgBuffer,
+                              all_map, outs.get("all_map"))
+        ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None (a null pointer for the kernels), not as a zero-filled image
+        if variant == PLANE:
+            ctx.mark_non_differentiable(radii, outs["observe"])
+            return outs["color"], radii, outs["observe"], outs["all_map"], outs["plane_depth"]
+        ctx.mark_non_differentiable(radii)
+        return (outs["color"], radii, outs["others"]) if variant == SURFEL else (outs["color"], radii)
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, *more):
+        rs, variant = ctx.raster_settings, ctx.variant
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer, imgBuffer,
+         all_map, all_map_pixels) = ctx.saved_tensors
+        pos = (variant, ctx.num_rendered, rs, radii, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map,
+               geomBuffer, binningBuffer, imgBuffer)
+        kw = dict(grad_color=grad_color)
+        if variant == SURFEL:
+            kw.update(grad_others=more[0])
+        elif variant == PLANE:               # more = the gradients of (out_observe, out_all_map, plane_depth)
+            kw.update(grad_all_map=more[1], grad_plane_depth=more[2])
+        g = _snapshot(rs.debug, pos[3:] + tuple(kw.values()), "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
+                      lambda: backward(*pos, all_map_pixels=all_map_pixels, **kw))
+        # (variant, means3D, means2D, means2D_abs, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map, raster_settings)
+        return (None, g["dL_dmeans3D"], g["dL_dmeans2D"], g.get("dL_dmeans2D_abs"), g["dL_dsh"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dscales"],
+                g["dL_drotations"], g["dL_dcov3D"], g.get("dL_dall_map"), None)
+
+
+def rasterize_gaussians(variant, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                        means2D_abs=None, all_map=None):
+    """-> the variant's tuple: EWA (color, radii), SURFEL (color, radii, allmap), PLANE (color, radii, out_observe, out_all_map, plane_depth)."""
+    return _RasterizeGaussians.apply(variant, means3D, means2D, means2D_abs, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     all_map, raster_settings)
+
+
+def exactly_one_of(shs, colors_precomp, scales, rotations, cov3D_precomp, *more, device=None):
+    """The argument checks every GaussianRasterizer.forward starts with -> the arguments, an empty tensor in the place of each None (on the
+    host as the EWA and PLANE references make it, on `device` as the surfel reference does)."""
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    return tuple(torch.empty(0, device=device) if x is None else x for x in (shs, colors_precomp, scales, rotations, cov3D_precomp) + more)

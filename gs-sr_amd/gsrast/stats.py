@@ -5,7 +5,7 @@ gssr/gaussian/pgsr_gaussian.py:164-172,157-161): three (PGSR: five) boolean-mask
 become one elementwise launch."""
 import torch
 
-from . import check, dev_f32, lib, ptr, stream_ptr
+from . import call, dev_f32
 
 
 def _acc(t, name, P):
@@ -40,5 +40,4 @@ def densification_stats_(max_radii2D, xyz_gradient_accum, denom, viewspace_grad,
         ob = None if out_observe is None else out_observe.reshape(-1).to(torch.int32).contiguous()
         if f.numel() != P or r.numel() != P or (ob is not None and ob.numel() != P):
             raise RuntimeError("densification_stats_: visibility_filter / radii / out_observe must have one entry per Gaussian")
-        check(lib().gsr_densify_stats(P, ptr(f), ptr(r), ptr(ob), ptr(g), int(g.shape[1]), ptr(ga), ptr(max_radii2D), ptr(xyz_gradient_accum),
-                                      ptr(denom), ptr(xyz_gradient_accum_abs), ptr(denom_abs), stream_ptr(g.device)), "densify_stats")
+        call("gsr_densify_stats", g.device, P, f, r, ob, g, int(g.shape[1]), ga, max_radii2D, xyz_gradient_accum, denom, xyz_gradient_accum_abs, denom_abs)

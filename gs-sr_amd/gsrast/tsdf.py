@@ -1,8 +1,10 @@
 """HIP TSDF voxel integration: the per-frame update of GaussianExtractor.extract_mesh_unbounded's
 compute_unbounded_tsdf (gssr/utils/mesh_utils.py:195-246) as one streaming kernel."""
+import ctypes as C
+
 import torch
 
-from . import last_error, lib, check, ptr, stream_ptr, dev_f32, TsdfSparse
+from . import last_error, lib, call, enqueue, one_device, scratch, ptr, dev_f32, TsdfSparse
 
 
 def tsdf_integrate_(points, full_proj_transform, depthmap, rgbmap, sdf_trunc, tsdfs, rgbs, weights):
@@ -22,9 +24,8 @@ def tsdf_integrate_(points, full_proj_transform, depthmap, rgbmap, sdf_trunc, ts
         tp = dev_f32(sdf_trunc, "sdf_trunc", allow_empty=False)
     else:
         st = float(sdf_trunc)
-    scratch = torch.empty((H * W, 4), dtype=torch.float32, device=pts.device)      # interleaved (r,g,b,d) texels
-    check(lib().gsr_tsdf_integrate(int(pts.shape[0]), ptr(pts), ptr(F), W, H, ptr(d), ptr(c), st, ptr(tp), ptr(tsdfs),
-                                   ptr(weights), ptr(rgbs), ptr(scratch), stream_ptr(pts.device)), "tsdf_integrate")
+    work = torch.empty((H * W, 4), dtype=torch.float32, device=pts.device)      # interleaved (r,g,b,d) texels
+    call("gsr_tsdf_integrate", pts.device, int(pts.shape[0]), pts, F, W, H, d, c, st, tp, tsdfs, weights, rgbs, work)
     return tsdfs, rgbs, weights
 
 
@@ -50,7 +51,6 @@ class DenseTSDFVolume:
 
     def integrate(self, rgb, depth, fx, fy, cx, cy, extrinsic, depth_trunc=float("inf"), quantize_rgb8=True):
         """rgb [3,H,W] in [0,1], depth [1,H,W] or [H,W], extrinsic 4x4 world->camera (row-major, Open3D convention)."""
-        import ctypes as C
         d = dev_f32(depth, "depth", allow_empty=False)
         c = dev_f32(rgb, "rgb", allow_empty=False)
         if quantize_rgb8:        # mesh_utils.py:170 converts colours to uint8 before fusion
@@ -60,10 +60,8 @@ class DenseTSDFVolume:
         H, W = int(d.shape[-2]), int(d.shape[-1])
         E = (C.c_float * 16)(*[float(v) for v in torch.as_tensor(extrinsic, dtype=torch.float32).reshape(-1).tolist()])
         o = (C.c_float * 3)(*self.origin)
-        check(lib().gsr_tsdf_integrate_dense(self.dims[0], self.dims[1], self.dims[2], o, self.voxel_length, self.sdf_trunc,
-                                             float(min(depth_trunc, 3.0e38)), W, H, ptr(d), ptr(c), float(fx), float(fy), float(cx),
-                                             float(cy), E, ptr(self.tsdf), ptr(self.weight), ptr(self.color),
-                                             stream_ptr(self.device)), "tsdf_integrate_dense")
+        call("gsr_tsdf_integrate_dense", self.device, self.dims[0], self.dims[1], self.dims[2], o, self.voxel_length, self.sdf_trunc,
+             float(min(depth_trunc, 3.0e38)), W, H, d, c, float(fx), float(fy), float(cx), float(cy), E, self.tsdf, self.weight, self.color)
         return self
 
     def merge_(self, group=None):
@@ -218,7 +216,6 @@ class ScalableTSDFVolume:
         self.chunk0_log2 = int(self.chunks[0].shape[0]).bit_length() - 1
 
     def _struct(self):
-        import ctypes as C
         arr = (C.c_void_p * TsdfSparse.MAX_CHUNKS)(*[c.data_ptr() for c in self.chunks])
         return TsdfSparse(ptr(self.keys), ptr(self.slot), ptr(self.coord), ptr(self.stamp), ptr(self.list), ptr(self.counters), ptr(self.mask), arr,
                           self.chunk0_log2, len(self.chunks), self.log2, self.cap, self.voxel_length, self.sdf_trunc)
@@ -244,12 +241,12 @@ class ScalableTSDFVolume:
         queue is full, by finish() or by any read of the volume, which then grows the pool and runs the refused frame AND every frame enqueued after it
         again, in order (a refused frame has integrated nothing, and neither has any frame behind it).  The volume keeps a reference to a deferred frame's
         rgb / depth until then: the caller must not overwrite those tensors before finish() (pass clones if its render buffers are reused)."""
-        import ctypes as C
         d = dev_f32(depth, "depth", allow_empty=False)
         c = dev_f32(rgb, "rgb", allow_empty=False)
         H, W = int(d.shape[-2]), int(d.shape[-1])
         if tuple(c.shape[-2:]) != (H, W) or c.numel() != 3 * H * W:
             raise RuntimeError("ScalableTSDFVolume.integrate: rgb must be [3,H,W] with the depth map's H, W")
+        one_device(("the volume", self.keys), ("depth", d), ("rgb", c))       # before a frame number or a status slot is taken
         E = torch.as_tensor(extrinsic, dtype=torch.float64).reshape(4, 4).cpu()
         Pm = torch.linalg.inv(E)
         Ea = (C.c_float * 12)(*[float(v) for v in E[:3].reshape(-1).tolist()])
@@ -279,7 +276,6 @@ class ScalableTSDFVolume:
         return self
 
     def _enqueue(self, f, sync):
-        import ctypes as C
         self.frame += 1
         used = {q["slot"] for q in self._queue}
         f["slot"] = next(i for i in range(self.MAX_IN_FLIGHT + 1) if i not in used) % self.MAX_IN_FLIGHT
@@ -288,22 +284,18 @@ class ScalableTSDFVolume:
             tex = self._tex = torch.empty((f["H"] * f["W"], 4), dtype=torch.float32, device=self.device)
         st = self._struct()
         self._status[f["slot"]].zero_()          # a call refused before it enqueues anything leaves the words alone: they must not be an earlier frame's
-        with torch.cuda.device(self.device):
-            rc = lib().gsr_tsdf_sparse_integrate2(C.byref(st), f["W"], f["H"], ptr(f["d"]), ptr(f["c"]), f["quant"], *f["intr"], f["Ea"], f["Pa"], f["dt"],
-                                                  self.stride, self.frame, ptr(tex), C.c_void_p(self._status[f["slot"]].data_ptr()),
-                                                  0 if sync else self.TSDF_NO_SYNC, stream_ptr(self.device))
+        rc = enqueue("gsr_tsdf_sparse_integrate2", self.device, C.byref(st), f["W"], f["H"], f["d"], f["c"], f["quant"], *f["intr"], f["Ea"], f["Pa"], f["dt"],
+                     self.stride, self.frame, tex, C.c_void_p(self._status[f["slot"]].data_ptr()), 0 if sync else self.TSDF_NO_SYNC)
         f["rc"] = rc
         f["err"] = last_error() if rc != 0 else ""      # the library's error text is one global string: by the time a deferred frame is looked at it may be another call's
 
     def _frame_rc(self, f):
         """-> (rc, error text, pool exhausted) of a frame whose status words are on the host.  Whether the pool ran out is read from the frame's own status
         word, never from the error text."""
-        import ctypes as C
         rc, msg = f["rc"], f["err"]
         if rc == 0 and "event" in f:
             st = self._struct()
-            with torch.cuda.device(self.device):
-                rc = lib().gsr_tsdf_sparse_status(C.byref(st), C.c_void_p(self._status[f["slot"]].data_ptr()), stream_ptr(self.device))
+            rc = enqueue("gsr_tsdf_sparse_status", self.device, C.byref(st), C.c_void_p(self._status[f["slot"]].data_ptr()))
             msg = last_error() if rc != 0 else ""
         return rc, msg, rc != 0 and int(self._status[f["slot"], 2]) != 0
 
@@ -357,7 +349,6 @@ class ScalableTSDFVolume:
     def _grow(self):
         """Doubles the unit pool: ONE MORE CHUNK of records (no voxel is copied, the volume never holds old and new pools side by side), larger coord / stamp /
         list / mask arrays with the allocated units' entries copied (140 B per unit), the hash table re-keyed with every unit in its old slot."""
-        import ctypes as C
         n = min(int(self.counters[0].item()), self.cap)
         old = (self.coord, self.stamp, self.mask)
         self._alloc(2 * self.cap, chunks=self.chunks)
@@ -365,8 +356,7 @@ class ScalableTSDFVolume:
             dst[:n].copy_(src[:n])
         self.counters[0] = n
         st = self._struct()
-        with torch.cuda.device(self.device):
-            check(lib().gsr_tsdf_sparse_rehash(C.byref(st), n, stream_ptr(self.device)), "tsdf_sparse_rehash")
+        call("gsr_tsdf_sparse_rehash", self.device, C.byref(st), n)
 
     @property
     def num_units(self):
@@ -394,43 +384,36 @@ class ScalableTSDFVolume:
         """-> (coords [n,3] int32, tsdf [n,16,16,16], weight [n,16,16,16], color [n,16,16,16,3]) of the allocated units as plain arrays
         (voxel index x-major, z fastest, like Open3D's UniformTSDFVolume::IndexOf).  Groups no frame ever wrote are zero-filled in the pools first
         (gsr_tsdf_sparse_materialize); the arrays are re-ordered COPIES of the brick-ordered pools."""
-        import ctypes as C
         n = self.num_units
         st = self._struct()
-        with torch.cuda.device(self.device):
-            check(lib().gsr_tsdf_sparse_materialize(C.byref(st), n, stream_ptr(self.device)), "tsdf_sparse_materialize")
+        call("gsr_tsdf_sparse_materialize", self.device, C.byref(st), n)
         # storage index bits, high to low: bx by bz (2 each) | x1 y1 x0 y0 | z (2)
         rec = brick_to_xmajor(self.records(n))                      # [n, 5, 16, 16, 16]
         return self.coord[:n], rec[:, 0], rec[:, 1], rec[:, 2:5].permute(0, 2, 3, 4, 1)
 
     def _mesh_count(self, min_weight=0.0):
         """First pass of the mesh extraction (gsr_tsdf_sparse_mesh_count): -> (n units, their output order, scratch, vertices, triangles)."""
-        import ctypes as C
         n = self.num_units
         if n == 0:
             return 0, None, None, 0, 0
         co = self.coord[:n].to(torch.int64) + (1 << 20)
         order = torch.argsort((co[:, 0] << 42) | (co[:, 1] << 21) | co[:, 2]).to(torch.int32)      # ascending (x, y, z): the mesh does not depend on the pool layout
         nbytes = int(lib().gsr_tsdf_sparse_mesh_scratch_bytes(n))
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        work = scratch(nbytes, self.device)
         counts = (C.c_uint64 * 2)()
         st = self._struct()
-        with torch.cuda.device(self.device):
-            check(lib().gsr_tsdf_sparse_mesh_count(C.byref(st), n, ptr(order), float(min_weight), ptr(scratch), nbytes, counts, stream_ptr(self.device)),
-                  "tsdf_sparse_mesh_count")
-        return n, order, scratch, int(counts[0]), int(counts[1])
+        call("gsr_tsdf_sparse_mesh_count", self.device, C.byref(st), n, order, float(min_weight), work, nbytes, counts)
+        return n, order, work, int(counts[0]), int(counts[1])
 
-    def _mesh_emit(self, n, order, scratch, V, T, min_weight=0.0):
+    def _mesh_emit(self, n, order, work, V, T, min_weight=0.0):
         """Second pass (gsr_tsdf_sparse_mesh_emit) behind `_mesh_count` with the same min_weight."""
-        import ctypes as C
         mesh = TriangleMesh(torch.empty((V, 3), dtype=torch.float32, device=self.device), torch.empty((V, 3), dtype=torch.float32, device=self.device),
                             torch.empty((T, 3), dtype=torch.int32, device=self.device))
         if V == 0 or T == 0:
             return mesh
         st = self._struct()
-        with torch.cuda.device(self.device):
-            check(lib().gsr_tsdf_sparse_mesh_emit(C.byref(st), n, ptr(order), float(min_weight), ptr(scratch), int(scratch.numel()), ptr(mesh.vertices),
-                                                  ptr(mesh.vertex_colors), ptr(mesh.triangles), stream_ptr(self.device)), "tsdf_sparse_mesh_emit")
+        call("gsr_tsdf_sparse_mesh_emit", self.device, C.byref(st), n, order, float(min_weight), work, int(work.numel()), mesh.vertices,
+             mesh.vertex_colors, mesh.triangles)
         return mesh
 
     def extract_triangle_mesh(self, min_weight=0.0):
@@ -440,14 +423,13 @@ class ScalableTSDFVolume:
         are a pure function of the volume's content (include/gsrast.h, gsr_tsdf_sparse_mesh_count): units in ascending coordinate order, voxels x-major,
         so volumes with equal content give byte-identical meshes whatever their insertion order, capacity or chunking."""
         self.finish()
-        n, order, scratch, V, T = self._mesh_count(min_weight)
-        return self._mesh_emit(n, order, scratch, V, T, min_weight)
+        n, order, work, V, T = self._mesh_count(min_weight)
+        return self._mesh_emit(n, order, work, V, T, min_weight)
 
     def merge_units_(self, coords, tsdf, weight, color, assume_unique=False):
         """self <- weighted merge with the given units (plain arrays shaped like `units()`, on this device).  The merge kernel runs one workgroup per
         listed unit, so a coordinate must not appear twice in one list: unless `assume_unique` the list is first fused with itself
         (merge_unit_lists: sort-unique + index_add)."""
-        import ctypes as C
         self.finish()
         n = int(coords.shape[0])
         if n == 0:
@@ -458,30 +440,29 @@ class ScalableTSDFVolume:
             n = int(coords.shape[0])
         co = coords.to(torch.int32).contiguous()
         t, w, c = (x.to(torch.float32).contiguous() for x in (tsdf, weight, color))
-        self._merge_call(lambda st: lib().gsr_tsdf_sparse_merge(C.byref(st), n, ptr(co), ptr(t), ptr(w), ptr(c), stream_ptr(self.device)), "tsdf_sparse_merge")
+        self._merge_call("gsr_tsdf_sparse_merge", n, co, t, w, c)
         return self
 
-    def _merge_call(self, call, what):
-        """One merge through the C ABI; "capacity exhausted" grows the pool and runs it again (the units the refused call allocated keep stamp 0 and are
+    def _merge_call(self, name, *args):
+        """One merge through the C ABI (entry point `name`, the volume's struct in front of args); "capacity exhausted" grows the pool and runs it
+        again (the units the refused call allocated keep stamp 0 and are
         found again), anything else leaves the volume usable and raises."""
         while True:
             st = self._struct()
-            with torch.cuda.device(self.device):
-                rc = call(st)
+            rc = enqueue(name, self.device, C.byref(st), *args)
             msg = last_error() if rc != 0 else ""
             if rc != 0 and self.auto_grow and int(self.counters[2].item()) != 0 and self.cap < (1 << 27):      # the volume's own overflow word, not the text
                 self._grow()
                 continue
             if rc != 0:
                 self._after_failure()
-                raise RuntimeError(f"{what}: {msg}")
+                raise RuntimeError(f"{name[4:]}: {msg}")
             self._allocated = min(int(self.counters[0].item()), self.cap)
             return
 
     def merge_from(self, other):
         """Fuses another volume (same voxel_length / sdf_trunc) into this one, e.g. the volumes of two tiles.  On one device the other volume's pools are
         read where they lie (gsr_tsdf_sparse_merge_volume: no export, no re-ordering, unwritten groups never touched)."""
-        import ctypes as C
         if abs(other.voxel_length - self.voxel_length) > 0 or abs(other.sdf_trunc - self.sdf_trunc) > 0:
             raise RuntimeError("merge_from: volumes must share voxel_length and sdf_trunc")
         self.finish()
@@ -489,7 +470,7 @@ class ScalableTSDFVolume:
         if other.device == self.device:
             if n:
                 so = other._struct()
-                self._merge_call(lambda st: lib().gsr_tsdf_sparse_merge_volume(C.byref(st), C.byref(so), n, stream_ptr(self.device)), "tsdf_sparse_merge_volume")
+                self._merge_call("gsr_tsdf_sparse_merge_volume", C.byref(so), n)
             return self
         co, t, w, c = other.units()
         return self.merge_units_(co.to(self.device), t.to(self.device), w.to(self.device), c.to(self.device), assume_unique=True)

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import check, dev_f32, lib, ptr, stream_ptr
+from . import call, dev_f32, lib, scratch
 from .tsdf import TriangleMesh
 
 DEFAULT_SLAB = 32       # x-planes per slab of extract_mesh_unbounded (33 are read): at 1023^2 points per plane 0.14 GB of samples and 0.14 GB of scratch
@@ -103,9 +103,7 @@ def lattice_points(xs, ys, zs, center, radius, voxel_size, device="cuda"):
     V = xs.numel() * ys.numel() * zs.numel()
     pts = torch.empty((V, 3), dtype=torch.float32, device=device)
     tr = torch.empty((V,), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        check(lib().gsr_unbounded_lattice_points(xs.numel(), ys.numel(), zs.numel(), ptr(xs), ptr(ys), ptr(zs), _center(center), _f32(radius),
-                                                 _f32(voxel_size), ptr(pts), ptr(tr), stream_ptr(device)), "unbounded_lattice_points")
+    call("gsr_unbounded_lattice_points", device, xs.numel(), ys.numel(), zs.numel(), xs, ys, zs, _center(center), _f32(radius), _f32(voxel_size), pts, tr)
     return pts, tr
 
 
@@ -133,11 +131,9 @@ def _lattice_groups(axes, c, radius, voxel_size, groups, state, device):
         if len(groups) > 1:
             tsdf.fill_(1.0)
             weight = torch.ones(shape, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        for P, d, _ in groups:
-            check(lib().gsr_unbounded_lattice_tsdf(shape[0], shape[1], shape[2], ptr(xs), ptr(ys), ptr(zs), c, _f32(radius), _f32(voxel_size),
-                                                   int(P.shape[0]), ptr(P), int(d.shape[-1]), int(d.shape[-2]), ptr(d), ptr(tsdf), ptr(weight),
-                                                   stream_ptr(device)), "unbounded_lattice_tsdf")
+    for P, d, _ in groups:
+        call("gsr_unbounded_lattice_tsdf", device, shape[0], shape[1], shape[2], xs, ys, zs, c, _f32(radius), _f32(voxel_size), int(P.shape[0]), P,
+             int(d.shape[-1]), int(d.shape[-2]), d, tsdf, weight)
     return tsdf if state is None else (tsdf, weight)
 
 
@@ -166,16 +162,14 @@ def _mc_slab(f, xs, ys, zs, own, vbase, tbase):
     device = f.device
     np_, ny, nz = (int(v) for v in f.shape)
     nbytes = int(L.gsr_unbounded_mc_scratch_bytes(np_, ny, nz))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    work = scratch(nbytes, device)
     counts = (C.c_uint64 * 2)()
-    with torch.cuda.device(device):
-        check(L.gsr_unbounded_mc_count(np_, ny, nz, own, ptr(f), ptr(scratch), nbytes, vbase, tbase, counts, stream_ptr(device)), "unbounded_mc_count")
-        nv, nt = int(counts[0]), int(counts[1])
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=device)
-        tris = torch.empty((nt, 3), dtype=torch.int32, device=device)
-        if nv or nt:
-            check(L.gsr_unbounded_mc_emit(np_, ny, nz, own, ptr(f), ptr(xs), ptr(ys), ptr(zs), ptr(scratch), nbytes, vbase, nv, nt, ptr(verts), ptr(tris),
-                                          stream_ptr(device)), "unbounded_mc_emit")
+    call("gsr_unbounded_mc_count", device, np_, ny, nz, own, f, work, nbytes, vbase, tbase, counts)
+    nv, nt = int(counts[0]), int(counts[1])
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=device)
+    tris = torch.empty((nt, 3), dtype=torch.int32, device=device)
+    if nv or nt:
+        call("gsr_unbounded_mc_emit", device, np_, ny, nz, own, f, xs, ys, zs, work, nbytes, vbase, nv, nt, verts, tris)
     return verts, tris
 
 
@@ -220,8 +214,7 @@ def finish_vertices(vertices, center, radius, max_range=32.0):
     v = vertices
     if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.dim() == 2 and v.shape[1] == 3):
         raise RuntimeError("vertices must be a contiguous float32 CUDA tensor [V,3]")
-    with torch.cuda.device(v.device):
-        check(lib().gsr_unbounded_finish(int(v.shape[0]), _center(center), _f32(radius), _f32(max_range), ptr(v), stream_ptr(v.device)), "unbounded_finish")
+    call("gsr_unbounded_finish", v.device, int(v.shape[0]), _center(center), _f32(radius), _f32(max_range), v)
     return v
 
 
@@ -237,9 +230,7 @@ def texture_vertices(vertices, voxel_size, full_proj, depth, rgb):
     V = 0 if v is None else int(v.shape[0])
     out = torch.empty((V, 3), dtype=torch.float32, device=P.device)
     if V:
-        with torch.cuda.device(P.device):
-            check(lib().gsr_unbounded_texture(V, ptr(v), _f32(voxel_size), int(P.shape[0]), ptr(P), int(d.shape[-1]), int(d.shape[-2]), ptr(d), ptr(c),
-                                              ptr(out), stream_ptr(P.device)), "unbounded_texture")
+        call("gsr_unbounded_texture", P.device, V, v, _f32(voxel_size), int(P.shape[0]), P, int(d.shape[-1]), int(d.shape[-2]), d, c, out)
     return out
 
 

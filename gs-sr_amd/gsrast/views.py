@@ -19,44 +19,28 @@ C <= num_views or fewer than num_views partners score above 0.
 
 Deviation.  In the reference a cosine that rounds above 1 gives NaN and silently poisons that pair's score (the row is then ranked with a NaN in it).
 Here any non-finite term, or a non-finite camera centre, raises RuntimeError."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import call, lib, one_device, raise_status, scratch, status_text, typed_tensor as _tensor
 
 ERR_NONFINITE, ERR_ABSENT, ERR_TABLE, ERR_OFFSETS, ERR_ID_RANGE = 1, 2, 4, 8, 16
 MAX_IMAGES = 16384                                        # GSR_VIEWS_MAX_IMAGES: a row of scores is held in LDS
 
 
+STATUS = {
+    ERR_NONFINITE: "a non-finite value: a camera centre or a term of a score is NaN or infinite (a point that coincides with a centre, or a cosine "
+                   "that rounds above 1)",
+    ERR_ABSENT: "a point id that two or more images observe is absent from the point table",
+    ERR_TABLE: "point_ids does not ascend strictly",
+    ERR_OFFSETS: "obs_offsets does not ascend from 0 to len(obs_ids)",
+    ERR_ID_RANGE: "wide_ids=False but an id has bits above 2^32",
+}
+
+
 def status_message(status):
     """The text of the status word of gsr_view_select."""
-    parts = []
-    if status & ERR_NONFINITE:
-        parts.append("a non-finite value: a camera centre or a term of a score is NaN or infinite (a point that coincides with a centre, or a cosine "
-                     "that rounds above 1)")
-    if status & ERR_ABSENT:
-        parts.append("a point id that two or more images observe is absent from the point table")
-    if status & ERR_TABLE:
-        parts.append("point_ids does not ascend strictly")
-    if status & ERR_OFFSETS:
-        parts.append("obs_offsets does not ascend from 0 to len(obs_ids)")
-    if status & ERR_ID_RANGE:
-        parts.append("wide_ids=False but an id has bits above 2^32")
-    return f"gsrast select_views: status {status}: " + "; ".join(parts or ["unknown bits"])
-
-
-def _tensor(t, name, dtype, shape):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{name}: expected {dtype} but found {t.dtype}")
-    if t.dim() != len(shape) or any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
-        raise RuntimeError(f"{name}: expected shape {[s if s is not None else '*' for s in shape]} but found {list(t.shape)}")
-    return t.detach().contiguous()
+    return status_text("select_views", status, STATUS)
 
 
 def _params(theta0, sigma1, sigma2, num_views):
@@ -89,25 +73,17 @@ def select_views(centers, obs_offsets, obs_ids, point_ids, point_xyz, theta0=5, 
     ids = _tensor(obs_ids, "obs_ids", torch.int64, (None,))
     pid = _tensor(point_ids, "point_ids", torch.int64, (None,))
     xyz = _tensor(point_xyz, "point_xyz", torch.float64, (pid.shape[0], 3))
-    for name, t in (("obs_offsets", off), ("obs_ids", ids), ("point_ids", pid), ("point_xyz", xyz)):
-        if t.device != cen.device:
-            raise RuntimeError(f"{name} must be on the device of centers")
+    dev = one_device(("centers", cen), ("obs_offsets", off), ("obs_ids", ids), ("point_ids", pid), ("point_xyz", xyz))
     M, Np, k = ids.shape[0], pid.shape[0], min(num_views, Cn)
-    L = lib()
-    dev = cen.device
     near_ids = torch.empty(Cn, k, dtype=torch.int32, device=dev)
     near_scores = torch.empty(Cn, k, dtype=torch.float64, device=dev)
     scores = torch.empty(Cn, Cn, dtype=torch.float64, device=dev) if return_scores else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    nbytes = int(L.gsr_view_select_scratch_bytes(M, Cn))
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(L.gsr_view_select(ptr(cen), Cn, ptr(off), ptr(ids) if M else None, M, ptr(pid) if Np else None, ptr(xyz) if Np else None, Np, theta0, sigma1, sigma2,
-                                k, 64 if wide_ids else 32, ptr(near_ids), ptr(near_scores), ptr(scores), ptr(scratch), nbytes, ptr(status), stream_ptr(dev)),
-              "view_select")
-        st = int(status.item()) & 0xFFFFFFFF              # the one host read
-    if st:
-        raise RuntimeError(status_message(st))
+    nbytes = int(lib().gsr_view_select_scratch_bytes(M, Cn))
+    work = scratch(nbytes, dev)
+    call("gsr_view_select", dev, cen, Cn, off, ids if M else None, M, pid if Np else None, xyz if Np else None, Np, theta0, sigma1, sigma2, k,
+         64 if wide_ids else 32, near_ids, near_scores, scores, work, nbytes, status)
+    raise_status("select_views", int(status.item()) & 0xFFFFFFFF, STATUS)      # the one host read
     return (near_ids, near_scores, scores) if return_scores else (near_ids, near_scores)
 
 

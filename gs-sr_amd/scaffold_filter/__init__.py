@@ -11,7 +11,7 @@ from typing import NamedTuple
 import torch
 import torch.nn as nn
 
-from gsrast import EWA, lib, check, ptr, stream_ptr, dev_f32, make_cfg
+from gsrast import EWA, call, one_device, dev_f32, make_cfg
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -53,6 +53,6 @@ class GaussianRasterizer(nn.Module):
             if (sc is None or ro is None) and cp is None:
                 raise RuntimeError("visible_filter needs scales+rotations or cov3D_precomp")
             cfg = make_cfg(EWA, P, raster_settings, 0, 0, False, keep)
-            check(lib().gsr_visible_filter(C.byref(cfg), ptr(m3), ptr(sc), ptr(ro), ptr(cp), ptr(radii),
-                                           stream_ptr(means3D.device)), "visible_filter")
+            one_device(("means3D", m3), *zip(("bg", "viewmatrix", "projmatrix", "campos"), keep))
+            call("gsr_visible_filter", means3D.device, C.byref(cfg), m3, sc, ro, cp, radii)
         return radii

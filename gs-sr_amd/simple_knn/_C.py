@@ -2,7 +2,7 @@
     distCUDA2(points float32 [P,3]) -> float32 [P]   mean squared distance to the 3 nearest neighbours."""
 import torch
 
-from gsrast import lib, check, ptr, stream_ptr, dev_f32
+from gsrast import lib, call, scratch, dev_f32
 
 
 def distCUDA2(points):
@@ -11,7 +11,6 @@ def distCUDA2(points):
     out = torch.zeros((P,), dtype=torch.float32, device=points.device)
     if P == 0:
         return out
-    L = lib()
-    scratch = torch.empty((max(int(L.gsr_dist2_scratch_bytes(P)), 1),), dtype=torch.uint8, device=points.device)
-    check(L.gsr_dist2(P, ptr(pts), ptr(out), ptr(scratch), scratch.numel(), stream_ptr(points.device)), "distCUDA2")
+    work = scratch(lib().gsr_dist2_scratch_bytes(P), points.device)
+    call("gsr_dist2", points.device, P, pts, out, work, work.numel(), what="distCUDA2")
     return out
