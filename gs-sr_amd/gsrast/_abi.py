@@ -212,6 +212,16 @@ FUNCTIONS = [
     ("gsr_partition_coverage_mask", cint, [vp, vp, i64, vp, i32, vp, i64, i32, vp, vp, vp, vp]),
     ("gsr_partition_coverage_rows_scratch_bytes", sz, [i64]),
     ("gsr_partition_coverage_rows", cint, [vp, i64, i32, P(i64), vp, vp, sz, vp]),
+    ("gsr_nearest_points_scratch_bytes", sz, [i64, i64]),
+    ("gsr_nearest_points", cint, [vp, i64, vp, i64, f32, vp, vp, vp, sz, vp]),
+    ("gsr_sample_surface_scratch_bytes", sz, [i64]),
+    ("gsr_sample_surface_count", cint, [vp, i64, vp, i64, f64, vp, sz, vp, vp]),
+    ("gsr_sample_surface_emit", cint, [vp, i64, vp, i64, f64, vp, sz, i64, vp, vp]),
+    ("gsr_voxel_downsample_scratch_bytes", sz, [i64]),
+    ("gsr_voxel_downsample_count", cint, [vp, i64, f64, vp, sz, vp, vp]),
+    ("gsr_voxel_downsample_emit", cint, [vp, i64, vp, sz, i64, vp, vp, vp]),
+    ("gsr_distance_stats_scratch_bytes", sz, [i64]),
+    ("gsr_distance_stats", cint, [vp, i64, f64, P(f64), i32, vp, vp, sz, vp]),
     ("gsr_debug_read", cint, [_cfg, i32, vp, vp, sz, vp, u32, vp, vp]),
     ("gsr_profile_enable", cint, [i32]),
     ("gsr_profile_read", cint, [P(f64), P(u64)]),

@@ -783,6 +783,50 @@ size_t gsr_partition_coverage_rows_scratch_bytes(int64_t Np);
 int gsr_partition_coverage_rows(const uint32_t* point_mask /*[Np,W]*/, int64_t Np, int32_t T, const int64_t* tile_offsets /*host [T + 1]*/, int64_t* rows,
                                 void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- surface distance: an extracted mesh against a ground-truth cloud (accuracy / completeness / Chamfer / F-score, the DTU and Tanks-and-Temples
+ * shape of evaluation; additions, no ABI bump).  The reference tree has no evaluation: nothing here has a counterpart there.  Counts < 2^31.  Point
+ * arrays are packed float32 [n,3] with no alignment beyond 4 bytes.  Scratch is caller-owned, 16-byte aligned, *_scratch_bytes() bytes.
+ * gsr_nearest_points: for every query q the nearest target t under
+ *     d2 = (dx*dx + dy*dy) + dz*dz,  dx = t.x - q.x, ...  float32, every operation rounded on its own;
+ *   among equal d2 the lowest target index; max_dist >= 0: a target counts only if d2 <= max_dist * max_dist (float32 product; equality stays in),
+ *   max_dist < 0: no cap.  A target with a non-finite coordinate never counts; a query with one, or with no counting target (n_target == 0
+ *   included), gets d2 = +inf and index = -1.  Bit for bit the all-pairs search, found through a uniform grid over the targets whose pruning is
+ *   conservative (csrc/gsr_chamfer.hip).  No status word and no host synchronisation.
+ * gsr_sample_surface_*: per triangle (a, b, c) of triangles [T,3] over vertices [V,3]: L2 = the largest of its three squared edge lengths (the
+ *   formula above), n = max(1, ceil(sqrt((double)L2) / spacing)), and n * n samples, the centroids of its n * n congruent sub-triangles: row
+ *   i = 0..n-1 holds the n - i "up" ones at u = (i + 1/3) / n, v = (j + 1/3) / n, j = 0..n-i-1, then the n - i - 1 "down" ones at
+ *   u = (i + 2/3) / n, v = (j + 2/3) / n;  p = (a + u * (b - a)) + v * (c - a) in double (1/3 and 2/3 the double quotients), every operation
+ *   rounded on its own, rounded to float32 once.  Triangle-major, then row, then that order.  count: record_dev [4 words] = {status, 0, total as
+ *   64 bits}; status GSR_CHAMFER_ERR_INDEX an index outside [0, V), GSR_CHAMFER_ERR_CAP an n above GSR_SAMPLE_MAX_N.  The caller reads the record
+ *   (its one host synchronisation), refuses a status or a total of 2^31 or more, and calls emit with the scratch as count left it: points [total,3].
+ * gsr_voxel_downsample_*: the cell of a point is floor((double)p / cell) per axis, inside [-2^20, 2^20) or GSR_CHAMFER_ERR_RANGE is set; per
+ *   occupied cell the point with the lowest index stays, points with a non-finite coordinate go.  count: record_dev [2] = {status, kept}; emit
+ *   (n_kept: the caller's copy of that count): points_out [n_kept,3] and index_out [n_kept] in ascending input index.
+ * gsr_distance_stats: over d = sqrt((double)d2[i]), clamped to max_dist where max_dist >= 0 (an infinite d2 then counts as max_dist): record_dev
+ *   [1 + GSR_CHAMFER_MAX_THRESHOLDS 64-bit words] = {the sum of d as a double, per threshold (HOST doubles) the number of d < threshold as
+ *   uint64}.  The sum runs in a fixed order that depends on n alone: bit-reproducible.  n == 0: all zero. */
+#define GSR_CHAMFER_ERR_INDEX 1u
+#define GSR_CHAMFER_ERR_CAP 2u
+#define GSR_CHAMFER_ERR_RANGE 4u
+#define GSR_SAMPLE_MAX_N 1024
+#define GSR_CHAMFER_MAX_THRESHOLDS 8
+size_t gsr_nearest_points_scratch_bytes(int64_t n_query, int64_t n_target);
+int gsr_nearest_points(const float* query /*[Q,3]*/, int64_t n_query, const float* target /*[T,3]*/, int64_t n_target, float max_dist, float* d2 /*[Q]*/,
+                       int32_t* index /*[Q]*/, void* scratch, size_t scratch_bytes, void* stream);
+size_t gsr_sample_surface_scratch_bytes(int64_t n_triangles);
+int gsr_sample_surface_count(const float* vertices /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles, double spacing,
+                             void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[4]*/, void* stream);
+int gsr_sample_surface_emit(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double spacing, const void* scratch,
+                            size_t scratch_bytes, int64_t total, float* points /*[total,3]*/, void* stream);
+size_t gsr_voxel_downsample_scratch_bytes(int64_t n_points);
+int gsr_voxel_downsample_count(const float* points /*[N,3]*/, int64_t n_points, double cell, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[2]*/,
+                               void* stream);
+int gsr_voxel_downsample_emit(const float* points, int64_t n_points, const void* scratch, size_t scratch_bytes, int64_t n_kept, float* points_out /*[n_kept,3]*/,
+                              int32_t* index_out /*[n_kept]*/, void* stream);
+size_t gsr_distance_stats_scratch_bytes(int64_t n);
+int gsr_distance_stats(const float* d2 /*[n]*/, int64_t n, double max_dist, const double* thresholds /*host [n_thresholds]*/, int32_t n_thresholds,
+                       void* record_dev /*[9 x 8 bytes]*/, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
