@@ -172,10 +172,9 @@ __global__ void __launch_bounds__(CF_BLOCK) k_cf_gather_hi(uint32_t n, const uin
     out[i] = src < n ? key_hi[src] : CF_BAD;
 }
 
-// The stable sort by the 64-bit key (key_hi[i] << 32 | key_lo[i]): the low word, then the gathered high word.  ka holds a copy of key_lo on entry.
-// Afterwards (*order)[i] = the point at place i and (*khi)[i] = its high word.
-struct CfSort { uint32_t *ka, *kb, *va, *vb, *key_lo, *key_hi, *hist; };
-static int cf_sort64(const CfSort& b, uint32_t n, uint32_t** khi, uint32_t** order, hipStream_t s)
+// The stable sort by the 64-bit key (key_hi[i] << 32 | key_lo[i]) (gsr_common.h; the mesh simplification sorts its cell keys with it too): the low
+// word, then the gathered high word.  ka holds a copy of key_lo on entry.  Afterwards (*order)[i] = the point at place i and (*khi)[i] = its high word.
+int gsr_sort64(const GsrSort64& b, uint32_t n, uint32_t** khi, uint32_t** order, hipStream_t s)
 {
     uint32_t *k0 = b.ka, *v0 = b.va, *k1 = b.kb, *v1 = b.vb;
     bool in_b = false;
@@ -394,11 +393,11 @@ __global__ void __launch_bounds__(CF_BLOCK) k_np_none(uint32_t Q, float* __restr
 }
 
 struct NpScratch {
-    CfSort so; uint32_t *bb, *nruns, *sums, *ustart, *dense; CfGrid* grid; unsigned long long* ukey; uint4* sorted; float* box;
+    GsrSort64 so; uint32_t *bb, *nruns, *sums, *ustart, *dense; CfGrid* grid; unsigned long long* ukey; uint4* sorted; float* box;
     uint32_t dense_cap; size_t bytes;
 };
 static uint32_t np_dense_cap(uint64_t T) { const uint64_t c = 4 * T; return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, CF_DENSE_MIN), 1ull << 30); }
-static void cf_carve_sort(GsrCarve& c, size_t n, CfSort* so)
+void gsr_sort64_carve(GsrCarve& c, size_t n, GsrSort64* so)
 {
     so->ka = c.take<uint32_t>(n); so->kb = c.take<uint32_t>(n); so->va = c.take<uint32_t>(n); so->vb = c.take<uint32_t>(n);
     so->key_lo = c.take<uint32_t>(n); so->key_hi = c.take<uint32_t>(n);
@@ -411,7 +410,7 @@ static NpScratch np_carve(uint64_t T, const void* base)
     m.bb = c.take<uint32_t>(64);                          // bb[0..6], nruns at word 8: one clear
     m.nruns = m.bb + 8;
     m.grid = c.take<CfGrid>(1);
-    cf_carve_sort(c, n, &m.so);
+    gsr_sort64_carve(c, n, &m.so);
     m.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     m.ustart = c.take<uint32_t>(n); m.ukey = c.take<unsigned long long>(n);
     m.sorted = c.take<uint4>(n); m.box = c.take<float>(6 * ((n + CF_CHUNK - 1) / CF_CHUNK));
@@ -450,7 +449,7 @@ extern "C" int gsr_nearest_points(const float* query, int64_t n_query, const flo
     hipLaunchKernelGGL(k_np_grid, dim3(1), dim3(64), 0, s, m.bb, max_dist, m.dense_cap, m.grid);
     hipLaunchKernelGGL(k_np_keys, dim3(gt), dim3(CF_BLOCK), 0, s, target, T, m.grid, m.so.key_lo, m.so.key_hi, m.so.ka);
     uint32_t *khi, *order;
-    if (cf_sort64(m.so, T, &khi, &order, s)) return 1;
+    if (gsr_sort64(m.so, T, &khi, &order, s)) return 1;
     const CfView v = { m.grid, m.nruns, m.ukey, m.ustart, m.dense, m.sorted, m.box };
     gsr_compact(CfRunOp{m.grid, khi, order, m.so.key_lo, m.ustart, m.ukey}, T, m.sums, m.nruns, s);
     hipLaunchKernelGGL(k_np_dense, dim3(gt), dim3(CF_BLOCK), 0, s, v, T, m.dense_cap, m.dense);
@@ -628,12 +627,12 @@ __global__ void __launch_bounds__(CF_BLOCK) k_vd_emit(const float* __restrict__ 
     for (int a = 0; a < 3; a++) out[3 * (size_t)j + a] = pts[3 * (size_t)src + a];
 }
 
-struct VdScratch { CfSort so; uint32_t *sums, *map; uint8_t* keep; size_t bytes; };
+struct VdScratch { GsrSort64 so; uint32_t *sums, *map; uint8_t* keep; size_t bytes; };
 static VdScratch vd_carve(uint64_t N, const void* base)
 {
     VdScratch m; GsrCarve c(base);
     const size_t n = N > 0 ? N : 1;
-    cf_carve_sort(c, n, &m.so);
+    gsr_sort64_carve(c, n, &m.so);
     m.sums = c.take<uint32_t>(gsr_compact_sums_words(n)); m.map = c.take<uint32_t>(n); m.keep = c.take<uint8_t>(n);
     m.bytes = c.bytes();
     return m;
@@ -657,7 +656,7 @@ extern "C" int gsr_voxel_downsample_count(const float* points, int64_t n_points,
     const uint32_t N = (uint32_t)n_points, g = gsr_div_up(N, CF_BLOCK);
     hipLaunchKernelGGL(k_vd_keys, dim3(g), dim3(CF_BLOCK), 0, s, points, N, cell, m.so.key_lo, m.so.key_hi, m.so.ka, record_dev);
     uint32_t *khi, *order;
-    if (cf_sort64(m.so, N, &khi, &order, s)) return 1;
+    if (gsr_sort64(m.so, N, &khi, &order, s)) return 1;
     hipLaunchKernelGGL(k_vd_flag, dim3(g), dim3(CF_BLOCK), 0, s, N, khi, order, m.so.key_lo, m.keep);
     gsr_rows_keep_scan(m.keep, N, m.sums, m.map, nullptr, record_dev + 1, s);
     return gsr_check_launch(who, s, false);

@@ -185,6 +185,12 @@ static inline size_t gsr_sort_hist_words(uint32_t nblk_1024, uint32_t NB) { retu
 int gsr_radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n, const uint32_t* n_dev,
                          int begin_bit, int end_bit, int bits_per_pass, bool identity_vals, uint32_t* hist,
                          bool* result_in_b, hipStream_t s, bool big_blocks = false, bool group0_zeroed = false);
+// The stable sort by a 64-bit key held as two words per element (gsr_chamfer.hip): the LSD sort on the low word, then on the gathered high word.  On
+// entry key_lo[i] / key_hi[i] hold the key of element i and ka a copy of key_lo; afterwards (*order)[i] = the element at place i and (*khi)[i] = its
+// high word (both point into ka / kb / va / vb).  gsr_sort64_carve takes the seven arrays for n elements out of a scratch block.
+struct GsrSort64 { uint32_t *ka, *kb, *va, *vb, *key_lo, *key_hi, *hist; };
+void gsr_sort64_carve(GsrCarve& c, size_t n, GsrSort64* so);
+int gsr_sort64(const GsrSort64& b, uint32_t n, uint32_t** khi, uint32_t** order, hipStream_t s);
 // In-place exclusive scan of `rows` rows of n words (row r at data + r * stride), one block per row, n small (block sums): k_scan_small.  Row r's
 // total goes to totals[r] and, where given, to totals2[r] as well.
 void gsr_scan_small(uint32_t* data, uint32_t n, uint32_t rows, uint32_t stride, uint32_t* totals, uint32_t* totals2, hipStream_t s);

@@ -194,7 +194,7 @@ def make_cfg(variant, P, settings, D, M, render_geo, keep):
     return cfg
 
 
-from .mesh import cluster_connected_triangles, post_process_mesh  # noqa: E402,F401  (gsrast.mesh needs the helpers above)
+from .mesh import cluster_connected_triangles, post_process_mesh, simplify_vertex_clustering  # noqa: E402,F401  (gsrast.mesh needs the helpers above)
 from .unbounded import extract_mesh_unbounded  # noqa: E402,F401
 from . import chamfer  # noqa: E402,F401
 from .chamfer import nearest_points, sample_surface, voxel_downsample, surface_distance  # noqa: E402,F401

@@ -187,6 +187,9 @@ FUNCTIONS = [
     ("gsr_mesh_cluster_triangles", cint, [vp, i64, i64, vp, vp, vp, vp, vp, sz, vp, vp]),
     ("gsr_mesh_filter_count", cint, [P(gsr_mesh_filter), vp, sz, vp, vp]),
     ("gsr_mesh_filter_emit", cint, [P(gsr_mesh_filter), vp, sz, P(u32), i32, P(gsr_rows_tensor), vp, vp]),
+    ("gsr_mesh_simplify_scratch_bytes", sz, [i64, i64, i32]),
+    ("gsr_mesh_simplify_count", cint, [vp, i64, vp, i64, f64, i32, vp, sz, vp, vp]),
+    ("gsr_mesh_simplify_emit", cint, [vp, vp, i64, i64, f64, i32, vp, sz, P(u32), vp, vp, vp, vp, vp]),
     ("gsr_unbounded_lattice_points", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, vp, vp, vp]),
     ("gsr_unbounded_lattice_tsdf", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, i32, vp, i32, i32, vp, vp, vp, vp]),
     ("gsr_unbounded_mc_scratch_bytes", sz, [i32, i32, i32]),

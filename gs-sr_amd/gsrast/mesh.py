@@ -4,8 +4,12 @@ extract_mesh.py:130-134 and extract_mesh_split.py:122-127 on what `extract_trian
 sources in include/gsrast.h, gsr_mesh_*; kernels in csrc/gsr_mesh_post.hip).  Every integer result is exact and a pure function of the index
 buffer; the cluster areas are added up with double atomics and are the one result that is not bit-reproducible.
 
+`simplify_vertex_clustering` is the step after it: the mesh made smaller by vertex clustering (csrc/gsr_mesh_simplify.hip), the role
+of Open3D's call of that name with semantics of this project's own -- no float atomics, every output bit-reproducible.
+
 There is no CPU path: a mesh that is not on a HIP device raises, like ScalableTSDFVolume."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -15,6 +19,10 @@ from ._abi import gsr_mesh_filter as Filter, gsr_rows_tensor as RowsTensor
 
 DROP_UNREFERENCED, DROP_DEGENERATE = 1, 2             # include/gsrast.h GSR_MESH_DROP_*
 ERR_INDEX, ERR_INTERNAL, ERR_KEEP = 1, 2, 4           # GSR_MESH_ERR_*
+ERR_RANGE, ERR_NONFINITE = 8, 16                      # GSR_MESH_ERR_* of the simplification
+SIMPLIFY_AVERAGE, SIMPLIFY_QUADRIC = 0, 1             # GSR_SIMPLIFY_*
+CONTRACTIONS = {"average": SIMPLIFY_AVERAGE, "quadric": SIMPLIFY_QUADRIC}
+CELL_LIMIT = 1 << 21                                  # simplify_vertex_clustering: cells per axis at most
 FLOOR = 50                                            # mesh_utils.py:41 "filter meshes smaller than 50"
 
 
@@ -112,6 +120,61 @@ def post_process_mesh(mesh, cluster_to_keep=1000):
         raise IndexError(f"index -{cluster_to_keep} is out of bounds for axis 0")
     v, c, t, _ = _filter(mesh, cluster_to_keep=int(cluster_to_keep), flags=DROP_UNREFERENCED | DROP_DEGENERATE)
     return TriangleMesh(v, c, t)
+
+
+def _simplify(mesh, voxel_size, contraction, want_map):
+    """One count call, the one host read-back, one emit call -> (vertices, vertex_colors, triangles, vertex_map or None, record)."""
+    if contraction not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {sorted(CONTRACTIONS)} but found {contraction!r}")
+    vs = float(voxel_size)
+    if not (vs > 0.0) or math.isinf(vs):
+        raise ValueError(f"voxel_size must be a positive finite number but found {voxel_size}")
+    v, c, t = _arrays(mesh)
+    T, V, dev, mode = int(t.shape[0]), int(v.shape[0]), t.device, CONTRACTIONS[contraction]
+    if V == 0 and T == 0:                                                 # nothing to launch
+        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.float32, device=dev),
+                torch.empty((0, 3), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev) if want_map else None, [0, 0, 0, 0])
+    nbytes = int(lib().gsr_mesh_simplify_scratch_bytes(T, V, mode))
+    if nbytes == 0:
+        raise RuntimeError(f"mesh: {T} triangles / {V} vertices: V and 3T must stay below 2^31; simplify the mesh in parts")
+    work = scratch(nbytes, dev)
+    record = torch.empty(8, dtype=torch.int32, device=dev)
+    call("gsr_mesh_simplify_count", dev, v if V else None, V, t if T else None, T, vs, mode, work, nbytes, record)
+    rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back
+    if rec[0] & ERR_NONFINITE:
+        raise RuntimeError("mesh: a vertex has a non-finite component (NaN or inf)")
+    if rec[0] & ERR_RANGE:
+        extent = (v.max(0).values.double() - v.min(0).values.double()).tolist()      # the error path reads back once more, to name the figures
+        raise RuntimeError(f"mesh: extent {extent} at voxel_size {vs} spans {max(extent) / vs:.4g} cells along an axis, the limit is 2^21 = {CELL_LIMIT}: "
+                           f"use a larger voxel_size or simplify the mesh in parts")
+    _raise_status(rec[0])
+    n_v, n_t = rec[1], rec[2]
+    nv, nc = torch.empty((n_v, 3), dtype=torch.float32, device=dev), torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+    tris = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev) if want_map else None
+    call("gsr_mesh_simplify_emit", dev, v if V else None, c if V else None, V, T, vs, mode, work, nbytes, (C.c_uint32 * 8)(*rec), nv if n_v else None,
+         nc if n_v else None, tris if n_t else None, vmap if want_map and V else None)
+    return nv, nc, tris, vmap, rec[:4]
+
+
+def simplify_vertex_clustering(mesh, voxel_size, contraction="average", return_map=False):
+    """The mesh made smaller by vertex clustering -> a new TriangleMesh on the mesh's device (and, with return_map, vertex_map int32 [V]: the new
+    index of every old vertex); the input is only read.  The role of Open3D's `simplify_vertex_clustering`; the semantics are this project's own
+    (include/gsrast.h, "mesh simplification") and every result is deterministic, bit for bit from run to run:
+      1. origin = float64(per-axis minimum over all vertices) - voxel_size / 2; the cell of a vertex is floor((float64(v) - origin) / voxel_size)
+      2. one new vertex per occupied cell, numbered by the cell's lowest member; unreferenced vertices are clustered like any other
+      3. position and colour: the float64 mean of the members, added in ascending vertex index, rounded to float32
+      4. contraction="quadric": the minimiser of the cell's summed triangle-plane quadrics instead, where it exists and lies inside the cell's
+         closed box; flat and edge-like cells fall back to the mean by themselves.  Colours are always the mean.
+      5. triangles are re-indexed; those with two equal indices go; each is rotated to start with its smallest index, and of equal triples the
+         first stays (a mirrored triple is another triple); survivors keep their order.
+    Raises RuntimeError for a mesh that spans 2^21 cells or more along an axis, for a non-finite vertex and for a triangle index outside [0, V);
+    ValueError for a voxel_size that is not a positive finite number or an unknown contraction.  An empty mesh gives an empty mesh.
+    Exactly ONE host read-back per call: the record {status, vertices, triangles, quadric cells} between the counting and the emitting pass."""
+    from .tsdf import TriangleMesh
+    nv, nc, tris, vmap, _ = _simplify(mesh, voxel_size, contraction, return_map)
+    out = TriangleMesh(nv, nc, tris)
+    return (out, vmap) if return_map else out
 
 
 def as_remove_mask(mask, n, device):

@@ -141,6 +141,12 @@ class TriangleMesh:
         from . import mesh as _m
         return self._filter_(flags=_m.DROP_DEGENERATE)
 
+    def simplify_vertex_clustering(self, voxel_size, contraction="average"):
+        """-> a NEW mesh, as Open3D's does: one vertex per occupied cell of size voxel_size (gsrast.mesh.simplify_vertex_clustering, which also
+        hands out the vertex map).  contraction: "average" or "quadric"."""
+        from . import mesh as _m
+        return _m.simplify_vertex_clustering(self, voxel_size, contraction)
+
     def __repr__(self):
         return f"TriangleMesh({int(self.vertices.shape[0])} vertices, {int(self.triangles.shape[0])} triangles, {self.vertices.device})"
 

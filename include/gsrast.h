@@ -617,6 +617,48 @@ int gsr_mesh_cluster_triangles(const int32_t* triangles, int64_t n_triangles, in
 int gsr_mesh_filter_count(const gsr_mesh_filter* f, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[8]*/, void* stream);
 int gsr_mesh_filter_emit(const gsr_mesh_filter* f, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/, int32_t n_rows,
                          const gsr_rows_tensor* rows, int32_t* triangles_out /*[T',3]*/, void* stream);
+/* ---- mesh simplification by vertex clustering (no ABI bump: additions only).
+ * The role of Open3D's simplify_vertex_clustering after post_process_mesh.  Open3D is not part of the reference tree and nothing here is held
+ * against it: the semantics below are this project's own, stated so that every result is deterministic (no float atomics: two runs give the same
+ * bits), and restated operation by operation in tests/simplify_truth.py.  Edge-collapse decimation is sequential by definition and is not offered.
+ * Inputs: vertices [V,3] float32, vertex_colors [V,3] float32, triangles [T,3] int32, voxel_size > 0 (double), contraction GSR_SIMPLIFY_*.
+ *   1. bound: lo = the per-axis minimum over ALL V vertices, referenced or not (a float32 minimum is exact in any order);
+ *      origin = (double)lo - 0.5 * voxel_size.
+ *   2. cell of a vertex: c = floor(((double)v - origin) / voxel_size) per axis: a float64 subtraction, an IEEE division, a floor.  Every component
+ *      must lie in [0, 2^21) or GSR_MESH_ERR_RANGE is set; a non-finite vertex component sets GSR_MESH_ERR_NONFINITE; a triangle index outside
+ *      [0, V) sets GSR_MESH_ERR_INDEX (such a triangle is never dereferenced).  With a status the results are to be discarded.
+ *   3. new vertices: one per occupied cell, numbered in ascending order of the cell's lowest member vertex index; vertex_map[v] (int32 [V]) is the
+ *      new index of old vertex v.  Unreferenced vertices are clustered like any other.
+ *   4. average position and colour: the float64 sum of the members' (double) values, added one after another in ascending vertex index, divided by
+ *      the count as a double, rounded to float32.  A vertex alone in its cell comes back bit for bit.  Colours are always the average.
+ *   5. GSR_SIMPLIFY_QUADRIC: for triangle t with corners a, b, c (in range), every operation in float64, rounded on its own, left to right:
+ *        a' = (double)a - origin, likewise b', c';  e1 = b' - a', e2 = c' - a';
+ *        N = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);  L = sqrt((Nx Nx + Ny Ny) + Nz Nz); L == 0 or non-finite: no contribution;
+ *        n = N / L per component, d = -((nx a'x + ny a'y) + nz a'z), p = (nx, ny, nz, d), w = L * 0.5, q_ij = w * (p_i * p_j) for the ten i <= j.
+ *      Each of the three corners adds q to the cell of that corner (two corners in one cell: twice); a cell's Q is the sum of its contributions in
+ *      ascending (triangle, corner) order, starting from 0.  With a_ij = Q_ij (i, j < 3) and r_i = -Q_i3:
+ *        c00 = a11 a22 - a12 a12, c01 = a02 a12 - a01 a22, c02 = a01 a12 - a02 a11, c11 = a00 a22 - a02 a02, c12 = a01 a02 - a00 a12,
+ *        c22 = a00 a11 - a01 a01;  det = (a00 c00 + a01 c01) + a02 c02;
+ *        x0 = ((c00 r0 + c01 r1) + c02 r2) / det, x1 = ((c01 r0 + c11 r1) + c12 r2) / det, x2 = ((c02 r0 + c12 r1) + c22 r2) / det.
+ *      The cell's position is (float)(origin + x) iff det is finite and > 0, every x_i is finite and (double)c_i * voxel_size <= x_i <=
+ *      ((double)c_i + 1.0) * voxel_size on every axis; otherwise the average of step 4.  The box test is the whole guard: no determinant threshold.
+ *   6. triangles: the three indices go through vertex_map; a triangle with two equal new indices goes; the rest are rotated so that the smallest
+ *      index comes first (orientation kept); of every distinct rotated triple only the occurrence with the lowest original triangle index stays (a
+ *      mirrored triple is another triple); survivors keep their original order and are emitted rotated.
+ *   7. limits: V < 2^31 and 3T < 2^31; gsr_mesh_simplify_scratch_bytes returns 0 beyond them (and for an unknown contraction).
+ * gsr_mesh_simplify_count: everything up to the counts; record_dev [8 words, 4 used] = {status, new vertices V', new triangles T', occupied cells
+ *   that took the quadric position}.  The caller reads the record (its one host synchronisation), allocates, and calls gsr_mesh_simplify_emit with
+ *   the HOST copy of the record and the UNMODIFIED scratch (>= gsr_mesh_simplify_scratch_bytes(T, V, contraction), caller-owned): it refuses a
+ *   non-zero status and writes vertices_out [V',3], vertex_colors_out [V',3], triangles_out [T',3] and, unless NULL, vertex_map_out [V].  Inputs
+ *   are only read; voxel_size and contraction are the same in both calls. */
+enum { GSR_SIMPLIFY_AVERAGE = 0, GSR_SIMPLIFY_QUADRIC = 1 };
+enum { GSR_MESH_ERR_RANGE = 8, GSR_MESH_ERR_NONFINITE = 16 };
+size_t gsr_mesh_simplify_scratch_bytes(int64_t n_triangles, int64_t n_vertices, int32_t contraction);
+int gsr_mesh_simplify_count(const float* vertices /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles, double voxel_size,
+                            int32_t contraction, void* scratch, size_t scratch_bytes, uint32_t* record_dev /*[8]*/, void* stream);
+int gsr_mesh_simplify_emit(const float* vertices, const float* vertex_colors /*[V,3]*/, int64_t n_vertices, int64_t n_triangles, double voxel_size,
+                           int32_t contraction, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/, float* vertices_out,
+                           float* vertex_colors_out, int32_t* triangles_out, int32_t* vertex_map_out /*[V] or NULL*/, void* stream);
 /* ---- the mesh of an unbounded scene (no ABI bump: additions only).
  * GaussianExtractor.extract_mesh_unbounded (gssr/utils/mesh_utils.py:181-277) over marching_cubes_with_contraction (gssr/utils/mcube_utils.py:17-95).
  * THE LATTICE.  Samples live in contracted coordinates on a dense lattice with ascending float32 axes xs[nx], ys[ny], zs[nz] (device arrays), flat
