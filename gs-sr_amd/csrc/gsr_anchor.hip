@@ -3,8 +3,8 @@
 // One growing level (ScaffoldGaussian.anchor_growing, gssr/gaussian/scaffold_gaussian.py:555-649; the loop body of OctreeGaussian.anchor_growing,
 // octree_gaussian.py:401-534): the reference compares every unique candidate cell against every anchor (O(U N), chunks of 4096), after a
 // torch.unique(dim=0) and before a scatter_max.  Here the cells of the admitted anchors and of the candidate slots are packed into 64-bit keys
-// (21 bits per axis + a tag bit that puts an occupied entry in front of the candidates of its cell) and sorted together by gsr_radix_sort_pairs
-// (low word, then stable by the high word); a run of equal cells that STARTS with a candidate is a new anchor.  Run heads come out in key
+// (21 bits per axis + a tag bit that puts an occupied entry in front of the candidates of its cell) and sorted together by the radix sort
+// (gsr_sort.h: low word, then stable by the high word); a run of equal cells that STARTS with a candidate is a new anchor.  Run heads come out in key
 // order = lexicographic signed (x, y, z), the order of torch.unique(dim=0).  Everything is integer compares and maxima: bitwise deterministic.
 //
 // This unit is built with -ffp-contract=off: the cell of a point is an integer output and must not depend on FMA contraction.
@@ -67,21 +67,14 @@ struct AncEntryOp {
     __device__ void place(uint32_t i, uint32_t pos) const { key_lo[pos] = (uint32_t)key; sort_keys[pos] = (uint32_t)key; key_hi[pos] = (uint32_t)(key >> 32); src[pos] = i; }
 };
 
-__global__ void __launch_bounds__(256) k_anc_gather_hi(const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_hi,
-                                                       uint32_t* __restrict__ keys)
-{
-    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    if (p < *n_dev) keys[p] = key_hi[perm[p]];
-}
-
 // sorted position p starts a new anchor iff it holds a candidate and the entry before it lies in another cell (occupied entries lead their run)
 __device__ __forceinline__ bool anc_is_head(uint32_t p, uint32_t n, const uint32_t* __restrict__ hi, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ key_lo)
 {
     if (p >= n) return false;
-    const uint64_t k = ((uint64_t)hi[p] << 32) | key_lo[perm[p]];
+    const uint64_t k = gsr_sort_key64(hi, perm, key_lo, p);
     if (!(k & 1u)) return false;
     if (p == 0) return true;
-    const uint64_t q = ((uint64_t)hi[p - 1] << 32) | key_lo[perm[p - 1]];
+    const uint64_t q = gsr_sort_key64(hi, perm, key_lo, p - 1);
     return (q >> 1) != (k >> 1);
 }
 
@@ -161,7 +154,7 @@ __global__ void __launch_bounds__(WEED_BLOCK) k_anc_weed_flag(gsr_anchor_level L
     uint32_t p = 0;
     if (active) {
         p = head_pos[q];
-        const uint64_t cellkey = (((uint64_t)hi[p] << 32) | key_lo[perm[p]]) >> 1;
+        const uint64_t cellkey = gsr_sort_key64(hi, perm, key_lo, p) >> 1;
         const int cx = (int)((cellkey >> 42) & 0x1FFFFFu) - ANC_BIAS, cy = (int)((cellkey >> 21) & 0x1FFFFFu) - ANC_BIAS, cz = (int)(cellkey & 0x1FFFFFu) - ANC_BIAS;
         const float ax = (float)cx * L.cell, ay = (float)cy * L.cell, az = (float)cz * L.cell;       // as k_anc_emit writes it
         px = ax + L.origin[0]; py = ay + L.origin[1]; pz = az + L.origin[2];
@@ -199,7 +192,7 @@ __global__ void __launch_bounds__(256) k_anc_emit(gsr_anchor_level L, uint32_t c
     if (q >= count || q >= counters[ANC_CNT_HEADS]) return;
     const uint32_t n = counters[ANC_CNT_ENTRIES];
     uint32_t p = head_pos[q];
-    const uint64_t cellkey = (((uint64_t)hi[p] << 32) | key_lo[perm[p]]) >> 1;
+    const uint64_t cellkey = gsr_sort_key64(hi, perm, key_lo, p) >> 1;
     if (f == 0) {
         const int cx = (int)((cellkey >> 42) & 0x1FFFFFu) - ANC_BIAS, cy = (int)((cellkey >> 21) & 0x1FFFFFu) - ANC_BIAS, cz = (int)(cellkey & 0x1FFFFFu) - ANC_BIAS;
         const float ax = (float)cx * L.cell, ay = (float)cy * L.cell, az = (float)cz * L.cell;
@@ -219,18 +212,26 @@ __global__ void __launch_bounds__(256) k_anc_emit(gsr_anchor_level L, uint32_t c
     new_feat[(size_t)q * F + f] = m;
 }
 
-struct AncScratch { uint32_t *sums, *key_lo, *key_hi, *src, *ka, *kb, *va, *vb, *hist, *counters; size_t bytes; };
+struct AncScratch { uint32_t *sums, *key_lo, *key_hi, *src, *counters; GsrSortBuf so; size_t bytes; };
 static AncScratch anc_carve(uint32_t cap, const void* base)
 {
     AncScratch a; GsrCarve c(base);
     const size_t n = cap > 0 ? cap : 1;
     a.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     a.key_lo = c.take<uint32_t>(n); a.key_hi = c.take<uint32_t>(n); a.src = c.take<uint32_t>(n);
-    a.ka = c.take<uint32_t>(n); a.kb = c.take<uint32_t>(n); a.va = c.take<uint32_t>(n); a.vb = c.take<uint32_t>(n);
-    a.hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256));
+    a.so = gsr_sort_carve(c, n);
     a.counters = c.take<uint32_t>(16);
     a.bytes = c.bytes();
     return a;
+}
+// What the two 32-bit sorts of anc_find leave where, for anc_find and for gsr_anchor_level_emit, which carves the same block again in a later call:
+// the high words and the order, and the free pair, which takes the run heads and (weed-out) their flags.
+struct AncSorted { uint32_t *hi, *perm, *head_pos, *flag; };
+static AncSorted anc_sorted(const AncScratch& a)
+{
+    GsrSort st(a.so);
+    st.advance(32); st.advance(32);
+    return { st.keys, st.order, st.free_keys, st.free_order };
 }
 
 static int anc_check(const gsr_anchor_level* lv, const char* who, uint32_t* cap)
@@ -285,25 +286,19 @@ static int anc_find(const char* who, const gsr_anchor_level* lv, const uint8_t* 
     hipStream_t s = (hipStream_t)stream;
     if (gsr_memset_async(a.counters, 0, 64, s)) { gsr_set_error("%s: counters", who); return 1; }
     if (cap) {
-        gsr_compact(AncEntryOp{*lv, occupy, status_dev, a.key_lo, a.key_hi, a.ka, a.src, 0}, cap, a.sums, a.counters + ANC_CNT_ENTRIES, s);
+        gsr_compact(AncEntryOp{*lv, occupy, status_dev, a.key_lo, a.key_hi, a.so.ka, a.src, 0}, cap, a.sums, a.counters + ANC_CNT_ENTRIES, s);
         const uint32_t* n_dev = a.counters + ANC_CNT_ENTRIES;
-        uint32_t *k0 = a.ka, *v0 = a.va, *k1 = a.kb, *v1 = a.vb;
-        bool in_b = false;
-        if (gsr_radix_sort_pairs(k0, v0, k1, v1, cap, n_dev, 0, 32, 8, true, a.hist, &in_b, s)) return 1;
-        if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
-        hipLaunchKernelGGL(k_anc_gather_hi, dim3(gsr_div_up(cap, 256)), dim3(256), 0, s, n_dev, v0, a.key_hi, k0);
-        if (gsr_radix_sort_pairs(k0, v0, k1, v1, cap, n_dev, 0, 32, 8, false, a.hist, &in_b, s)) return 1;
-        if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
-        // both sorts run 4 passes of 8 bits: the order ends in (ka, va), the run heads go to kb -- gsr_anchor_level_emit relies on it
-        if (k0 != a.ka || v0 != a.va) { gsr_set_error("%s: unexpected sort buffer parity", who); return 1; }
-        gsr_compact(AncHeadOp{n_dev, a.ka, a.va, a.key_lo, a.kb}, cap, a.sums, a.counters + ANC_CNT_HEADS, s);
+        GsrSort st(a.so);
+        if (st.sort(cap, n_dev, 32, true, s) || gsr_sort_next_word(st, cap, n_dev, GsrWordFromArray{a.key_hi}, s)) return 1;
+        const AncSorted so = anc_sorted(a);
+        gsr_compact(AncHeadOp{n_dev, so.hi, so.perm, a.key_lo, so.head_pos}, cap, a.sums, a.counters + ANC_CNT_HEADS, s);
         if (weed) {
-            // heads <= candidate slots; key_hi (consumed by the gather) keeps the unweeded heads, vb (free: the order ended in ka / va) the flags
+            // heads <= candidate slots; key_hi (consumed by the second sort) keeps the unweeded heads, the free order the flags
             const uint32_t worst = (uint32_t)lv->N0 * (uint32_t)lv->k;
             if (worst) {
-                hipLaunchKernelGGL(k_anc_weed_flag, dim3(gsr_div_up(worst, WEED_BLOCK)), dim3(WEED_BLOCK), 0, s, *lv, W, weed->lv, a.counters, a.ka, a.va, a.key_lo,
-                                   a.kb, a.key_hi, a.vb);
-                gsr_compact(AncWeedOp{a.counters, a.vb, a.key_hi, a.kb}, cap, a.sums, a.counters + ANC_CNT_FOUND, s);
+                hipLaunchKernelGGL(k_anc_weed_flag, dim3(gsr_div_up(worst, WEED_BLOCK)), dim3(WEED_BLOCK), 0, s, *lv, W, weed->lv, a.counters, so.hi, so.perm, a.key_lo,
+                                   so.head_pos, a.key_hi, so.flag);
+                gsr_compact(AncWeedOp{a.counters, so.flag, a.key_hi, so.head_pos}, cap, a.sums, a.counters + ANC_CNT_FOUND, s);
             }
         }
     }
@@ -349,7 +344,8 @@ extern "C" int gsr_anchor_level_emit(const gsr_anchor_level* lv, const void* scr
     if (!new_anchor || (lv->F && !new_feat)) { gsr_set_error("anchor_level_emit: new_anchor / new_feat is NULL"); return 1; }
     const size_t threads = (size_t)count * (size_t)(lv->F > 0 ? lv->F : 1);
     if ((threads + 255) / 256 >= (1ull << 31)) { gsr_set_error("anchor_level_emit: count * F too large"); return 1; }
-    hipLaunchKernelGGL(k_anc_emit, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lv, count, a.counters, a.ka, a.va, a.key_lo, a.src,
-                       a.kb, new_anchor, new_feat);
+    const AncSorted so = anc_sorted(a);
+    hipLaunchKernelGGL(k_anc_emit, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lv, count, a.counters, so.hi, so.perm, a.key_lo, a.src,
+                       so.head_pos, new_anchor, new_feat);
     return gsr_check_launch("anchor_level_emit", (hipStream_t)stream, false);
 }

@@ -7,7 +7,7 @@
 //               axis, and whether the dense table applies -- all on the device, the host never learns them.  A coordinate's cell is
 //               clamp(floor((double(x) - min) * (1 / h)), 0, n - 1): evaluated in double, monotone in x, the same function for targets and queries.
 //   sort        key = ix | iy << 21 | iz << 42 (non-finite targets: all ones, they end up behind the Tf finite ones); the project's stable LSD
-//               sort on the low word, then on the gathered high word (as gsr_anchor.hip); run heads by gsr_compact -> ukey[r], ustart[r].
+//               sort on the low word, then on the high word (gsr_sort.h); run heads by gsr_compact -> ukey[r], ustart[r].
 //   table       run of a cell: dense[cell] = r + 1 while nx ny nz <= the table's capacity (4 T words, at least 4096), else a binary search of ukey.
 //   query       one thread per query, its cell clamped into the grid (a query outside the box starts at the nearest boundary cell), shells of
 //               cells of Chebyshev radius k = 0, 1, ...  A cell / a shell is skipped / the search ends when
@@ -164,33 +164,10 @@ __global__ void __launch_bounds__(CF_BLOCK) k_np_keys(const float* __restrict__ 
     key_lo[i] = lo; key_hi[i] = hi; sort_lo[i] = lo;
 }
 
-__global__ void __launch_bounds__(CF_BLOCK) k_cf_gather_hi(uint32_t n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ key_hi, uint32_t* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * CF_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = order[i];
-    out[i] = src < n ? key_hi[src] : CF_BAD;
-}
-
-// The stable sort by the 64-bit key (key_hi[i] << 32 | key_lo[i]) (gsr_common.h; the mesh simplification sorts its cell keys with it too): the low
-// word, then the gathered high word.  ka holds a copy of key_lo on entry.  Afterwards (*order)[i] = the point at place i and (*khi)[i] = its high word.
-int gsr_sort64(const GsrSort64& b, uint32_t n, uint32_t** khi, uint32_t** order, hipStream_t s)
-{
-    uint32_t *k0 = b.ka, *v0 = b.va, *k1 = b.kb, *v1 = b.vb;
-    bool in_b = false;
-    if (gsr_radix_sort_pairs(k0, v0, k1, v1, n, nullptr, 0, 32, 8, true, b.hist, &in_b, s)) return 1;
-    if (in_b) { std::swap(k0, k1); std::swap(v0, v1); }
-    hipLaunchKernelGGL(k_cf_gather_hi, dim3(gsr_div_up(n, CF_BLOCK)), dim3(CF_BLOCK), 0, s, n, v0, b.key_hi, k0);
-    if (gsr_radix_sort_pairs(k0, v0, k1, v1, n, nullptr, 0, 32, 8, false, b.hist, &in_b, s)) return 1;
-    if (in_b) { std::swap(k0, k1); std::swap(v0, v1); }
-    *khi = k0; *order = v0;
-    return 0;
-}
-
 // the heads of the runs of equal keys among the first Tf places: ustart[r] = the place, ukey[r] = the key
 struct CfRunOp {
     const CfGrid* grid; const uint32_t *khi, *order, *key_lo; uint32_t* ustart; unsigned long long* ukey;
-    __device__ unsigned long long key(uint32_t i) const { return ((unsigned long long)khi[i] << 32) | key_lo[order[i]]; }
+    __device__ unsigned long long key(uint32_t i) const { return gsr_sort_key64(khi, order, key_lo, i); }
     __device__ bool keep(uint32_t i) const { return i < grid->Tf && (i == 0u || key(i) != key(i - 1u)); }
     __device__ void place(uint32_t i, uint32_t p) const { ustart[p] = i; ukey[p] = key(i); }
 };
@@ -393,16 +370,10 @@ __global__ void __launch_bounds__(CF_BLOCK) k_np_none(uint32_t Q, float* __restr
 }
 
 struct NpScratch {
-    GsrSort64 so; uint32_t *bb, *nruns, *sums, *ustart, *dense; CfGrid* grid; unsigned long long* ukey; uint4* sorted; float* box;
+    GsrSortBuf so; uint32_t *key_lo, *key_hi, *bb, *nruns, *sums, *ustart, *dense; CfGrid* grid; unsigned long long* ukey; uint4* sorted; float* box;
     uint32_t dense_cap; size_t bytes;
 };
 static uint32_t np_dense_cap(uint64_t T) { const uint64_t c = 4 * T; return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, CF_DENSE_MIN), 1ull << 30); }
-void gsr_sort64_carve(GsrCarve& c, size_t n, GsrSort64* so)
-{
-    so->ka = c.take<uint32_t>(n); so->kb = c.take<uint32_t>(n); so->va = c.take<uint32_t>(n); so->vb = c.take<uint32_t>(n);
-    so->key_lo = c.take<uint32_t>(n); so->key_hi = c.take<uint32_t>(n);
-    so->hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256));
-}
 static NpScratch np_carve(uint64_t T, const void* base)
 {
     NpScratch m; GsrCarve c(base);
@@ -410,7 +381,7 @@ static NpScratch np_carve(uint64_t T, const void* base)
     m.bb = c.take<uint32_t>(64);                          // bb[0..6], nruns at word 8: one clear
     m.nruns = m.bb + 8;
     m.grid = c.take<CfGrid>(1);
-    gsr_sort64_carve(c, n, &m.so);
+    m.so = gsr_sort_carve(c, n); m.key_lo = c.take<uint32_t>(n); m.key_hi = c.take<uint32_t>(n);
     m.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     m.ustart = c.take<uint32_t>(n); m.ukey = c.take<unsigned long long>(n);
     m.sorted = c.take<uint4>(n); m.box = c.take<float>(6 * ((n + CF_CHUNK - 1) / CF_CHUNK));
@@ -447,13 +418,13 @@ extern "C" int gsr_nearest_points(const float* query, int64_t n_query, const flo
     if (gsr_memset_async(m.bb, 0, 256, s) || gsr_memset_async(m.dense, 0, (size_t)m.dense_cap * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
     hipLaunchKernelGGL(k_np_bbox, dim3(std::min(gsr_div_up(T, CF_BLOCK * 16u), 512u)), dim3(CF_BLOCK), 0, s, target, T, m.bb);
     hipLaunchKernelGGL(k_np_grid, dim3(1), dim3(64), 0, s, m.bb, max_dist, m.dense_cap, m.grid);
-    hipLaunchKernelGGL(k_np_keys, dim3(gt), dim3(CF_BLOCK), 0, s, target, T, m.grid, m.so.key_lo, m.so.key_hi, m.so.ka);
-    uint32_t *khi, *order;
-    if (gsr_sort64(m.so, T, &khi, &order, s)) return 1;
+    hipLaunchKernelGGL(k_np_keys, dim3(gt), dim3(CF_BLOCK), 0, s, target, T, m.grid, m.key_lo, m.key_hi, m.so.ka);
+    GsrSort st(m.so);                                     // the low word, then the high word
+    if (st.sort(T, nullptr, 32, true, s) || gsr_sort_next_word(st, T, nullptr, GsrWordFromArray{m.key_hi}, s)) return 1;
     const CfView v = { m.grid, m.nruns, m.ukey, m.ustart, m.dense, m.sorted, m.box };
-    gsr_compact(CfRunOp{m.grid, khi, order, m.so.key_lo, m.ustart, m.ukey}, T, m.sums, m.nruns, s);
+    gsr_compact(CfRunOp{m.grid, st.keys, st.order, m.key_lo, m.ustart, m.ukey}, T, m.sums, m.nruns, s);
     hipLaunchKernelGGL(k_np_dense, dim3(gt), dim3(CF_BLOCK), 0, s, v, T, m.dense_cap, m.dense);
-    hipLaunchKernelGGL(k_np_gather, dim3(gsr_div_up(T, CF_CHUNK)), dim3(CF_CHUNK), 0, s, target, T, m.grid, order, m.sorted, m.box);
+    hipLaunchKernelGGL(k_np_gather, dim3(gsr_div_up(T, CF_CHUNK)), dim3(CF_CHUNK), 0, s, target, T, m.grid, st.order, m.sorted, m.box);
     const float md2 = max_dist >= 0.f ? max_dist * max_dist : __builtin_inff();
     hipLaunchKernelGGL(k_np_query, dim3(gq), dim3(CF_BLOCK), 0, s, query, Q, v, md2, d2, index);
     return gsr_check_launch(who, s, false);
@@ -627,12 +598,12 @@ __global__ void __launch_bounds__(CF_BLOCK) k_vd_emit(const float* __restrict__ 
     for (int a = 0; a < 3; a++) out[3 * (size_t)j + a] = pts[3 * (size_t)src + a];
 }
 
-struct VdScratch { GsrSort64 so; uint32_t *sums, *map; uint8_t* keep; size_t bytes; };
+struct VdScratch { GsrSortBuf so; uint32_t *key_lo, *key_hi, *sums, *map; uint8_t* keep; size_t bytes; };
 static VdScratch vd_carve(uint64_t N, const void* base)
 {
     VdScratch m; GsrCarve c(base);
     const size_t n = N > 0 ? N : 1;
-    gsr_sort64_carve(c, n, &m.so);
+    m.so = gsr_sort_carve(c, n); m.key_lo = c.take<uint32_t>(n); m.key_hi = c.take<uint32_t>(n);
     m.sums = c.take<uint32_t>(gsr_compact_sums_words(n)); m.map = c.take<uint32_t>(n); m.keep = c.take<uint8_t>(n);
     m.bytes = c.bytes();
     return m;
@@ -654,10 +625,10 @@ extern "C" int gsr_voxel_downsample_count(const float* points, int64_t n_points,
     if (gsr_memset_async(record_dev, 0, 8, s)) { gsr_set_error("%s: clear", who); return 1; }
     if (n_points == 0) return gsr_check_launch(who, s, false);
     const uint32_t N = (uint32_t)n_points, g = gsr_div_up(N, CF_BLOCK);
-    hipLaunchKernelGGL(k_vd_keys, dim3(g), dim3(CF_BLOCK), 0, s, points, N, cell, m.so.key_lo, m.so.key_hi, m.so.ka, record_dev);
-    uint32_t *khi, *order;
-    if (gsr_sort64(m.so, N, &khi, &order, s)) return 1;
-    hipLaunchKernelGGL(k_vd_flag, dim3(g), dim3(CF_BLOCK), 0, s, N, khi, order, m.so.key_lo, m.keep);
+    hipLaunchKernelGGL(k_vd_keys, dim3(g), dim3(CF_BLOCK), 0, s, points, N, cell, m.key_lo, m.key_hi, m.so.ka, record_dev);
+    GsrSort st(m.so);
+    if (st.sort(N, nullptr, 32, true, s) || gsr_sort_next_word(st, N, nullptr, GsrWordFromArray{m.key_hi}, s)) return 1;
+    hipLaunchKernelGGL(k_vd_flag, dim3(g), dim3(CF_BLOCK), 0, s, N, st.keys, st.order, m.key_lo, m.keep);
     gsr_rows_keep_scan(m.keep, N, m.sums, m.map, nullptr, record_dev + 1, s);
     return gsr_check_launch(who, s, false);
 }

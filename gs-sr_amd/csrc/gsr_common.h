@@ -172,25 +172,8 @@ int gsr_memset_async(void* p, int byte_value, size_t nbytes, hipStream_t s);
 int gsr_launch_preprocess_bwd(const gsr_cfg* cfg, const gsr_inputs* in, const int32_t* radii, GeomView g,
                               float* acc, const gsr_in_grads* ig, bool leave_zero, hipStream_t s);
 
-// generic device-wide primitives (gsr_binning.hip)
-// Histogram scratch of the sort: [2 group-histogram buffers of NB * groups words][block histograms NB * nblk], groups = ceil(nblk / 16).
-// `group0_zeroed`: the caller's preceding kernel already zeroed the first NB * groups words (gsr_sort_group_words) -- otherwise a memset does.
-#define GSR_SORT_GROUP 16
-#ifndef GSR_SORT_MAX_GROUPS
-#define GSR_SORT_MAX_GROUPS 96        // re-measured with 1024-key blocks (tools/ab_sort_groups.sh): binning 0.0678 / 0.0688 / 0.071 ms at 96 / 48 / 160 groups
-#endif
-static inline uint32_t gsr_sort_blocks(uint32_t n, bool big_blocks) { return gsr_div_up(n, GSR_SORT_THREADS * (big_blocks ? 16u : (uint32_t)GSR_SORT_ITEMS)); }
-static inline uint32_t gsr_sort_group_words(uint32_t n, bool big_blocks, uint32_t NB) { return NB * gsr_div_up(gsr_sort_blocks(n, big_blocks), GSR_SORT_GROUP); }
-static inline size_t gsr_sort_hist_words(uint32_t nblk_1024, uint32_t NB) { return (size_t)NB * nblk_1024 + 2 * (size_t)NB * (nblk_1024 / GSR_SORT_GROUP + 1); }
-int gsr_radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n, const uint32_t* n_dev,
-                         int begin_bit, int end_bit, int bits_per_pass, bool identity_vals, uint32_t* hist,
-                         bool* result_in_b, hipStream_t s, bool big_blocks = false, bool group0_zeroed = false);
-// The stable sort by a 64-bit key held as two words per element (gsr_chamfer.hip): the LSD sort on the low word, then on the gathered high word.  On
-// entry key_lo[i] / key_hi[i] hold the key of element i and ka a copy of key_lo; afterwards (*order)[i] = the element at place i and (*khi)[i] = its
-// high word (both point into ka / kb / va / vb).  gsr_sort64_carve takes the seven arrays for n elements out of a scratch block.
-struct GsrSort64 { uint32_t *ka, *kb, *va, *vb, *key_lo, *key_hi, *hist; };
-void gsr_sort64_carve(GsrCarve& c, size_t n, GsrSort64* so);
-int gsr_sort64(const GsrSort64& b, uint32_t n, uint32_t** khi, uint32_t** order, hipStream_t s);
+// generic device-wide primitives, each with the unit that holds it.  What a caller of the radix sort (gsr_binning.hip) needs is in gsr_sort.h.
+#include "gsr_sort.h"
 // In-place exclusive scan of `rows` rows of n words (row r at data + r * stride), one block per row, n small (block sums): k_scan_small.  Row r's
 // total goes to totals[r] and, where given, to totals2[r] as well.
 void gsr_scan_small(uint32_t* data, uint32_t n, uint32_t rows, uint32_t stride, uint32_t* totals, uint32_t* totals2, hipStream_t s);

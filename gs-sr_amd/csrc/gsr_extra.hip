@@ -419,17 +419,15 @@ __global__ void __launch_bounds__(256) k_knn_dist(int P, const float* __restrict
     out[me] = (b0 + b1 + b2) / 3.0f;
 }
 
-struct KnnScratch { uint32_t *mm, *keys_a, *keys_b, *vals_a, *vals_b, *hist; float* boxes; size_t bytes; };
+struct KnnScratch { uint32_t* mm; GsrSortBuf so; float* boxes; size_t bytes; };
 static KnnScratch knn_carve(int P, void* base)
 {
-    KnnScratch k; char* p = (char*)base;
+    KnnScratch k; GsrCarve c(base);
     const size_t n = (size_t)(P > 0 ? P : 1);
-    const uint32_t nblk = gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), nbox = gsr_div_up((uint32_t)n, GSR_KNN_BOX);
-    auto take = [&](size_t bytes) { char* r = p; p += gsr_align(bytes); return r; };
-    k.mm = (uint32_t*)take(64); k.keys_a = (uint32_t*)take(n * 4); k.keys_b = (uint32_t*)take(n * 4);
-    k.vals_a = (uint32_t*)take(n * 4); k.vals_b = (uint32_t*)take(n * 4);
-    k.hist = (uint32_t*)take(gsr_sort_hist_words(nblk, 256) * 4); k.boxes = (float*)take((size_t)nbox * 6 * 4);
-    k.bytes = (size_t)(p - (char*)base);
+    k.mm = c.take<uint32_t>(16);
+    k.so = gsr_sort_carve(c, n);
+    k.boxes = c.take<float>((size_t)gsr_div_up((uint32_t)n, GSR_KNN_BOX) * 6);
+    k.bytes = c.bytes();
     return k;
 }
 extern "C" size_t gsr_dist2_scratch_bytes(int32_t P) { return knn_carve(P, nullptr).bytes; }
@@ -442,10 +440,10 @@ extern "C" int gsr_dist2(int32_t P, const float* points, float* out, void* scrat
     const int nbox = (int)gsr_div_up((uint32_t)P, GSR_KNN_BOX);
     hipLaunchKernelGGL(k_knn_init, dim3(1), dim3(64), 0, s, k.mm);
     hipLaunchKernelGGL(k_knn_minmax, dim3(min(1024u, gsr_div_up((uint32_t)P, 256))), dim3(256), 0, s, P, points, k.mm);
-    hipLaunchKernelGGL(k_knn_morton, dim3(gsr_div_up((uint32_t)P, 256)), dim3(256), 0, s, P, points, k.mm, k.keys_a);
-    bool in_b = false;
-    if (gsr_radix_sort_pairs(k.keys_a, k.vals_a, k.keys_b, k.vals_b, (uint32_t)P, nullptr, 0, 30, 8, true, k.hist, &in_b, s)) return 1;
-    const uint32_t* order = in_b ? k.vals_b : k.vals_a;
+    hipLaunchKernelGGL(k_knn_morton, dim3(gsr_div_up((uint32_t)P, 256)), dim3(256), 0, s, P, points, k.mm, k.so.ka);
+    GsrSort st(k.so);
+    if (st.sort((uint32_t)P, nullptr, 30, true, s)) return 1;
+    const uint32_t* order = st.order;
     hipLaunchKernelGGL(k_knn_boxes, dim3(nbox), dim3(GSR_KNN_BOX), 0, s, P, points, order, k.boxes);
     hipLaunchKernelGGL(k_knn_dist, dim3(gsr_div_up((uint32_t)P, 256)), dim3(256), 0, s, P, points, order, k.boxes, nbox, out);
     return gsr_check_launch("dist2", s, false);

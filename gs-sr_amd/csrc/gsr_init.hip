@@ -16,7 +16,7 @@
 //   arrays      k_sel_hist: the same select over an array (gsr_select, gsr_common.h): floats with their sign-magnitude patterns folded to unsigned
 //               order, or uint32 complemented for a descending order (the mesh filter's k-th largest cluster, gsr_mesh_post.hip).
 //   voxels      per cell size: key = rint((p - init_pos) / cell) per axis (IEEE divide, half to even), three stable LSD sorts (z, y, x) of the
-//               sign-biased int32 keys with gsr_radix_sort_pairs, run heads by the keep scan; the heads' point indices stay in scratch for the emit.
+//               sign-biased int32 keys, each word regenerated through the order (gsr_sort.h), run heads by the keep scan; the heads' point indices stay in scratch for the emit.
 // lerp: ATen's Lerp.h, w < 0.5 ? a + w * (b - a) : b - (b - a) * (1 - w), every operation rounded on its own (PRE_FLAGS: no contraction).  That is what
 // torch.quantile gives on the CPU at ATen's DEFAULT dispatch level; its AVX2 / AVX512 kernels fuse the product-sum and differ in the last bit in about
 // one case in a hundred (measured).
@@ -334,18 +334,23 @@ template <typename T> __device__ __forceinline__ int32_t vu_key(T p, T init, T c
 }
 __device__ __forceinline__ uint32_t vu_bias(int32_t k) { return (uint32_t)k ^ 0x80000000u; }
 
-// keys[i] = biased key of axis `axis` of point perm[i] (i itself where perm is NULL)
+// the biased key of axis `axis` of point src < N, one word of the sort's key (gsr_sort_next_word); its error bits go to *status
+template <typename T> struct VuAxisOp {
+    VuArgs<T> a; int axis; uint32_t* status;
+    __device__ uint32_t operator()(uint32_t src) const
+    {
+        uint32_t err = 0;
+        const int32_t k = vu_key<T>(a.points[3 * (size_t)src + axis], a.init[axis], a.cell, &err);
+        if (err) atomicOr(status, err);
+        return vu_bias(k);
+    }
+};
+// the first word, in point order: keys[i] = op(i)
 template <typename T>
-__global__ void __launch_bounds__(VU_BLOCK) k_vu_keys(VuArgs<T> a, int axis, const uint32_t* __restrict__ perm, uint32_t* __restrict__ keys, uint32_t* __restrict__ status)
+__global__ void __launch_bounds__(VU_BLOCK) k_vu_keys(VuAxisOp<T> op, uint32_t* __restrict__ keys)
 {
     const uint32_t i = blockIdx.x * VU_BLOCK + threadIdx.x;
-    if (i >= a.N) return;
-    const uint32_t src = perm ? perm[i] : i;
-    uint32_t err = 0;
-    int32_t k = 0;
-    if (src < a.N) k = vu_key<T>(a.points[3 * (size_t)src + axis], a.init[axis], a.cell, &err);
-    keys[i] = vu_bias(k);
-    if (err) atomicOr(status, err);
+    if (i < op.a.N) keys[i] = op(i);
 }
 
 template <typename T> __device__ __forceinline__ void vu_key3(const VuArgs<T>& a, uint32_t src, int32_t* k)
@@ -399,13 +404,12 @@ __global__ void __launch_bounds__(VU_BLOCK) k_vu_emit(VuArgs<T> a, VuLevels lv, 
     level[j] = l;
 }
 
-struct VuScratch { uint32_t *ka, *kb, *va, *vb, *hist, *sums, *map, *heads; uint8_t* flag; size_t bytes; };
+struct VuScratch { GsrSortBuf so; uint32_t *sums, *map, *heads; uint8_t* flag; size_t bytes; };
 static VuScratch vu_carve(uint32_t N, int32_t L, const void* base)
 {
     VuScratch v; GsrCarve c(base);
     const size_t n = N > 0 ? N : 1;
-    v.ka = c.take<uint32_t>(n); v.kb = c.take<uint32_t>(n); v.va = c.take<uint32_t>(n); v.vb = c.take<uint32_t>(n);
-    v.hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)n, GSR_SORT_BLOCK), 256));
+    v.so = gsr_sort_carve(c, n);
     v.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     v.map = c.take<uint32_t>(n); v.flag = c.take<uint8_t>(n);
     v.heads = c.take<uint32_t>(n * (size_t)(L > 0 ? L : 1));
@@ -443,16 +447,14 @@ static int vu_count(const char* who, const void* points, uint32_t N, int32_t L, 
     const uint32_t g = gsr_div_up(N, VU_BLOCK);
     for (int l = 0; l < L; l++) {
         a.cell = (T)cell[l];
-        uint32_t *k0 = v.ka, *v0 = v.va, *k1 = v.kb, *v1 = v.vb;
-        for (int axis = 2; axis >= 0; axis--) {           // stable LSD: z, then y, then x -> rows ascend by x, then y, then z
-            hipLaunchKernelGGL((k_vu_keys<T>), dim3(g), dim3(VU_BLOCK), 0, s, a, axis, axis == 2 ? (const uint32_t*)nullptr : (const uint32_t*)v0, k0, record_dev);
-            bool in_b = false;
-            if (gsr_radix_sort_pairs(k0, v0, k1, v1, N, nullptr, 0, 32, 8, axis == 2, v.hist, &in_b, s)) return 1;
-            if (in_b) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
-        }
-        hipLaunchKernelGGL((k_vu_flag<T>), dim3(g), dim3(VU_BLOCK), 0, s, a, v0, v.flag);
+        GsrSort st(v.so);                                 // stable LSD: z, then y, then x -> rows ascend by x, then y, then z
+        hipLaunchKernelGGL((k_vu_keys<T>), dim3(g), dim3(VU_BLOCK), 0, s, VuAxisOp<T>{a, 2, record_dev}, st.keys);
+        if (st.sort(N, nullptr, 32, true, s)) return 1;
+        for (int axis = 1; axis >= 0; axis--)
+            if (gsr_sort_next_word(st, N, nullptr, VuAxisOp<T>{a, axis, record_dev}, s)) return 1;
+        hipLaunchKernelGGL((k_vu_flag<T>), dim3(g), dim3(VU_BLOCK), 0, s, a, st.order, v.flag);
         gsr_rows_keep_scan(v.flag, N, v.sums, v.map, nullptr, record_dev + 1 + l, s);
-        hipLaunchKernelGGL(k_vu_heads, dim3(g), dim3(VU_BLOCK), 0, s, record_dev + 1 + l, N, v.map, v0, v.heads + (size_t)l * N);
+        hipLaunchKernelGGL(k_vu_heads, dim3(g), dim3(VU_BLOCK), 0, s, record_dev + 1 + l, N, v.map, st.order, v.heads + (size_t)l * N);
     }
     return gsr_check_launch(who, s, false);
 }

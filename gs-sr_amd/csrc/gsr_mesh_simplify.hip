@@ -6,7 +6,7 @@
 //   bound       per-axis minimum of all V vertices by integer atomicMax on the complemented order-preserving bit pattern (as gsr_chamfer.hip);
 //               origin = (double)lo - 0.5 voxel.
 //   cells       c = floor(((double)v - origin) / voxel) per axis, inside [0, 2^21) or GSR_MESH_ERR_RANGE; key = cx | cy << 21 | cz << 42, sorted with the
-//               vertex index as value by the stable 64-bit sort of gsr_chamfer.hip (gsr_sort64: low word, then the gathered high word): the members of a cell stand in a run in
+//               vertex index as value by the stable sort on the low word, then on the high word (gsr_sort.h): the members of a cell stand in a run in
 //               ascending vertex index, its head is the lowest member.
 //   numbering   head flags in VERTEX order -> keep scan (gsr_rows_keep_scan): rank of a head = its new index, first[p] = the head of new vertex p.  The
 //               heads in SORTED order -> gsr_compact: ustart[r].  One thread per run writes vertex_map of its members.  No second sort.
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(MS_BLOCK) k_ms_keys(const float* __restrict__ 
     key_lo[i] = lo; key_hi[i] = hi; sort_lo[i] = lo;
 }
 
-// What the sort left, as every later kernel reads it: place i holds vertex order[i] with key (khi[i], key_lo[order[i]])
+// What the sort left, as every later kernel reads it: place i holds vertex order[i] with key (khi[i], key_lo[order[i]]) -- gsr_sort_key64, compared word by word with a bound on order[i]
 struct MsRuns {
     const uint32_t *khi, *order, *key_lo; uint32_t V;
     __device__ bool head(uint32_t i) const
@@ -339,11 +339,11 @@ __global__ void __launch_bounds__(MS_BLOCK) k_ms_emit_map(const uint32_t* __rest
 // ------------------------------------------------------------------------------------------------ C ABI (include/gsrast.h)
 struct MsScratch {
     uint32_t *bb, *n_qruns;                       // bb[0..2], the corner runs at word 8: one clear
-    GsrSort64 so;                                 // the vertices' sort (gsr_sort64)
+    GsrSortBuf so; uint32_t *key_lo, *key_hi;     // the vertices' sort and the two words of their keys
     uint32_t *sums, *order, *ustart, *rank, *first, *vmap;      // order .. vmap stay until the emit
     uint8_t *vflag, *qflag, *live, *tkeep;
     float* qpos;
-    uint32_t *ca, *cb, *cva, *cvb, *chist, *qstart;      // the corners' sort (quadric only)
+    GsrSortBuf cso; uint32_t* qstart;             // the corners' sort (quadric only)
     uint32_t *rt, *tmap;
     MsTable tb;
     size_t bytes;
@@ -353,14 +353,13 @@ static MsScratch ms_carve(uint64_t T, uint64_t V, bool quadric, const void* base
     MsScratch m; GsrCarve c(base);
     const size_t v = V > 0 ? V : 1, t = T > 0 ? T : 1, h = 3 * t, n = std::max(v, quadric ? h : t);
     m.bb = c.take<uint32_t>(64); m.n_qruns = m.bb + 8;
-    gsr_sort64_carve(c, v, &m.so);
+    m.so = gsr_sort_carve(c, v); m.key_lo = c.take<uint32_t>(v); m.key_hi = c.take<uint32_t>(v);
     m.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     m.order = c.take<uint32_t>(v); m.ustart = c.take<uint32_t>(v); m.rank = c.take<uint32_t>(v); m.first = c.take<uint32_t>(v); m.vmap = c.take<uint32_t>(v);
     m.vflag = c.take<uint8_t>(v); m.qflag = c.take<uint8_t>(v); m.live = c.take<uint8_t>(t); m.tkeep = c.take<uint8_t>(t);
     m.qpos = c.take<float>(quadric ? 3 * v : 1);
     const size_t hq = quadric ? h : 1;
-    m.ca = c.take<uint32_t>(hq); m.cb = c.take<uint32_t>(hq); m.cva = c.take<uint32_t>(hq); m.cvb = c.take<uint32_t>(hq); m.qstart = c.take<uint32_t>(hq);
-    m.chist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up((uint32_t)hq, GSR_SORT_BLOCK), 256));
+    m.cso = gsr_sort_carve(c, hq); m.qstart = c.take<uint32_t>(hq);
     m.rt = c.take<uint32_t>(3 * t); m.tmap = c.take<uint32_t>(t);
     uint32_t slots = 64;
     while (slots < 2 * t) slots <<= 1;            // 2 t < 2^31: at most 2^31 slots
@@ -398,10 +397,10 @@ extern "C" int gsr_mesh_simplify_count(const float* vertices, int64_t n_vertices
     if (gsr_memset_async(record_dev, 0, 32, s) || gsr_memset_async(m.bb, 0, 256, s)) { gsr_set_error("%s: clear", who); return 1; }
     if (V > 0) {
         hipLaunchKernelGGL(k_ms_bound, dim3(std::min(gsr_div_up(V, MS_BLOCK * 16u), 512u)), dim3(MS_BLOCK), 0, s, vertices, V, m.bb, record_dev + MS_R_STATUS);
-        hipLaunchKernelGGL(k_ms_keys, dim3(ms_grid(V)), dim3(MS_BLOCK), 0, s, vertices, V, m.bb, voxel_size, m.so.key_lo, m.so.key_hi, m.so.ka, record_dev + MS_R_STATUS);
-        uint32_t *khi, *order;
-        if (gsr_sort64(m.so, V, &khi, &order, s)) return 1;
-        const MsRuns ru = { khi, order, m.so.key_lo, V };
+        hipLaunchKernelGGL(k_ms_keys, dim3(ms_grid(V)), dim3(MS_BLOCK), 0, s, vertices, V, m.bb, voxel_size, m.key_lo, m.key_hi, m.so.ka, record_dev + MS_R_STATUS);
+        GsrSort st(m.so);
+        if (st.sort(V, nullptr, 32, true, s) || gsr_sort_next_word(st, V, nullptr, GsrWordFromArray{m.key_hi}, s)) return 1;
+        const MsRuns ru = { st.keys, st.order, m.key_lo, V };
         hipLaunchKernelGGL(k_ms_heads, dim3(ms_grid(V)), dim3(MS_BLOCK), 0, s, ru, m.vflag, m.order);
         gsr_rows_keep_scan(m.vflag, V, m.sums, m.first, m.rank, record_dev + MS_R_V, s);
         gsr_compact(MsRunOp{ru, m.ustart}, V, m.sums, m.n_qruns + 1, s);      // the same count once more, into a spare word
@@ -411,14 +410,12 @@ extern "C" int gsr_mesh_simplify_count(const float* vertices, int64_t n_vertices
         int bits = 1;
         while (bits < 32 && (1ull << bits) < (unsigned long long)V) bits++;
         if (gsr_memset_async(m.qflag, 0, V, s)) { gsr_set_error("%s: clear", who); return 1; }
-        hipLaunchKernelGGL(k_ms_corner_keys, dim3(ms_grid(H)), dim3(MS_BLOCK), 0, s, triangles, H, V, m.vmap, m.ca);
-        uint32_t *k0 = m.ca, *v0 = m.cva;
-        bool in_b = false;
-        if (gsr_radix_sort_pairs(m.ca, m.cva, m.cb, m.cvb, H, nullptr, 0, bits, 8, true, m.chist, &in_b, s)) return 1;
-        if (in_b) { k0 = m.cb; v0 = m.cvb; }
-        gsr_compact(MsCornerRunOp{k0, m.qstart}, H, m.sums, m.n_qruns, s);
+        hipLaunchKernelGGL(k_ms_corner_keys, dim3(ms_grid(H)), dim3(MS_BLOCK), 0, s, triangles, H, V, m.vmap, m.cso.ka);
+        GsrSort cst(m.cso);
+        if (cst.sort(H, nullptr, bits, true, s)) return 1;
+        gsr_compact(MsCornerRunOp{cst.keys, m.qstart}, H, m.sums, m.n_qruns, s);
         const MsMesh mesh = { vertices, triangles, V, T, voxel_size };
-        hipLaunchKernelGGL(k_ms_quadric, dim3(ms_grid(std::min(H, V))), dim3(MS_BLOCK), 0, s, mesh, m.bb, m.n_qruns, m.qstart, k0, v0, m.first, m.so.key_lo, m.so.key_hi, m.qpos,
+        hipLaunchKernelGGL(k_ms_quadric, dim3(ms_grid(std::min(H, V))), dim3(MS_BLOCK), 0, s, mesh, m.bb, m.n_qruns, m.qstart, cst.keys, cst.order, m.first, m.key_lo, m.key_hi, m.qpos,
                            m.qflag, record_dev);
     }
     if (T > 0) {

@@ -6,7 +6,7 @@
 //
 //   flatten     the observations are image-major ([offsets[a], offsets[a + 1]) belongs to image a); the entries != -1 are compacted in that order
 //               (gsr_compact.h) with their image and the low word of their id
-//   sort        stable LSD radix sort by id (gsr_radix_sort_pairs): the low word, then -- only where the caller says ids need it (id_bits = 64) -- the
+//   sort        stable LSD radix sort by id (gsr_sort.h): the low word, then -- only where the caller says ids need it (id_bits = 64) -- the
 //               sign-biased high word.  The input is image-major and the sort stable, so a run of equal ids is a track with its images ascending and
 //               the repeats of one image adjacent
 //   entries     heads of the runs of equal (id, image): entry e = one image of one track, multiplicity = the length of its run; tracks = heads of
@@ -35,7 +35,8 @@
 #define VW_CNT_TRACKS 2
 
 struct VwScratch {
-    uint32_t *cnt, *sums, *map, *cimg, *ka, *kb, *va, *vb, *hist, *simg, *emap, *eimg, *tmap, *etrack, *tpi, *ioff;
+    uint32_t *cnt, *sums, *map, *cimg, *simg, *emap, *eimg, *tmap, *etrack, *tpi, *ioff;
+    GsrSortBuf so;            // both sorts: the observations by id, then the entries by image
     int64_t* sid;
     size_t bytes;
 };
@@ -45,8 +46,7 @@ static VwScratch vw_carve(uint32_t n, uint32_t C, const void* base)
     v.cnt = c.take<uint32_t>(16);
     v.sums = c.take<uint32_t>(gsr_compact_sums_words(n));
     v.map = c.take<uint32_t>(n); v.cimg = c.take<uint32_t>(n);
-    v.ka = c.take<uint32_t>(n); v.kb = c.take<uint32_t>(n); v.va = c.take<uint32_t>(n); v.vb = c.take<uint32_t>(n);
-    v.hist = c.take<uint32_t>(gsr_sort_hist_words(gsr_div_up(n, GSR_SORT_BLOCK), 256));
+    v.so = gsr_sort_carve(c, n);
     v.sid = c.take<int64_t>(n); v.simg = c.take<uint32_t>(n);
     v.emap = c.take<uint32_t>(n); v.eimg = c.take<uint32_t>(n); v.tmap = c.take<uint32_t>(n); v.etrack = c.take<uint32_t>(n); v.tpi = c.take<uint32_t>(n);
     v.ioff = c.take<uint32_t>((size_t)C + 1);
@@ -108,15 +108,11 @@ struct VwTrackOp {
     __device__ void place(uint32_t e, uint32_t t) const { tmap[t] = e; }
 };
 
-// the sign-biased high words of the ids in the order the low-word sort left: ascending as int64 after the second sort
-__global__ void __launch_bounds__(VW_BLOCK) k_vw_high(const int64_t* __restrict__ ids, const uint32_t* __restrict__ map, const uint32_t* __restrict__ order, uint32_t n,
-                                                      const uint32_t* __restrict__ cnt, uint32_t* __restrict__ key)
-{
-    const uint32_t i = blockIdx.x * VW_BLOCK + threadIdx.x;
-    if (i >= min(n, cnt[VW_CNT_OBS])) return;
-    const uint32_t p = order[i];
-    key[i] = p < n ? (uint32_t)((uint64_t)ids[map[p]] >> 32) ^ 0x80000000u : 0u;
-}
+// the sign-biased high word of the id of compacted observation p (gsr_sort_next_word): ascending as int64 after the second sort
+struct VwHighOp {
+    const int64_t* ids; const uint32_t* map;
+    __device__ uint32_t operator()(uint32_t p) const { return (uint32_t)((uint64_t)ids[map[p]] >> 32) ^ 0x80000000u; }
+};
 
 __global__ void __launch_bounds__(VW_BLOCK) k_vw_sorted(const int64_t* __restrict__ ids, const uint32_t* __restrict__ map, const uint32_t* __restrict__ cimg,
                                                         const uint32_t* __restrict__ order, uint32_t n, const uint32_t* __restrict__ cnt, int64_t* __restrict__ sid,
@@ -332,32 +328,25 @@ extern "C" int gsr_view_select(const double* centres, int32_t C, const int64_t* 
 
     hipLaunchKernelGGL(k_vw_check, dim3(gsr_div_up(std::max(3u * Cu, (uint32_t)Np), VW_BLOCK)), dim3(VW_BLOCK), 0, s, centres, Cu, obs_offsets, M, point_ids, (uint32_t)Np,
                        status_dev);
-    gsr_compact(VwValidOp{obs_ids, obs_offsets, (uint32_t)M, Cu, id_bits, v.map, v.cimg, v.ka, status_dev}, n, v.sums, v.cnt + VW_CNT_OBS, s);
-    uint32_t *k0 = v.ka, *v0 = v.va, *k1 = v.kb, *v1 = v.vb;
-    bool in_b = false;
-    if (gsr_radix_sort_pairs(k0, v0, k1, v1, n, v.cnt + VW_CNT_OBS, 0, 32, 8, true, v.hist, &in_b, s)) return 1;
-    if (in_b) { std::swap(k0, k1); std::swap(v0, v1); }
-    if (id_bits == 64) {
-        hipLaunchKernelGGL(k_vw_high, dim3(g), dim3(VW_BLOCK), 0, s, obs_ids, v.map, v0, n, v.cnt, k0);
-        if (gsr_radix_sort_pairs(k0, v0, k1, v1, n, v.cnt + VW_CNT_OBS, 0, 32, 8, false, v.hist, &in_b, s)) return 1;
-        if (in_b) { std::swap(k0, k1); std::swap(v0, v1); }
-    }
-    hipLaunchKernelGGL(k_vw_sorted, dim3(g), dim3(VW_BLOCK), 0, s, obs_ids, v.map, v.cimg, v0, n, v.cnt, v.sid, v.simg);
+    gsr_compact(VwValidOp{obs_ids, obs_offsets, (uint32_t)M, Cu, id_bits, v.map, v.cimg, v.so.ka, status_dev}, n, v.sums, v.cnt + VW_CNT_OBS, s);
+    GsrSort by_id(v.so);
+    if (by_id.sort(n, v.cnt + VW_CNT_OBS, 32, true, s)) return 1;
+    if (id_bits == 64 && gsr_sort_next_word(by_id, n, v.cnt + VW_CNT_OBS, VwHighOp{obs_ids, v.map}, s)) return 1;
+    hipLaunchKernelGGL(k_vw_sorted, dim3(g), dim3(VW_BLOCK), 0, s, obs_ids, v.map, v.cimg, by_id.order, n, v.cnt, v.sid, v.simg);
     // the sort buffers are free again: the entries' image keys go to ka
-    gsr_compact(VwEntryOp{v.sid, v.simg, v.cnt, n, v.emap, v.eimg, v.ka}, n, v.sums, v.cnt + VW_CNT_ENTRIES, s);
+    gsr_compact(VwEntryOp{v.sid, v.simg, v.cnt, n, v.emap, v.eimg, v.so.ka}, n, v.sums, v.cnt + VW_CNT_ENTRIES, s);
     gsr_compact(VwTrackOp{v.sid, v.emap, v.cnt, n, v.tmap}, n, v.sums, v.cnt + VW_CNT_TRACKS, s);
     hipLaunchKernelGGL(k_vw_tracks, dim3(g), dim3(VW_BLOCK), 0, s, v.sid, v.emap, v.tmap, n, v.cnt, point_ids, (uint32_t)Np, v.etrack, v.tpi,
                        status_dev);
     int img_bits = 1;
     while (img_bits < 31 && (1u << img_bits) < Cu) img_bits++;
-    k0 = v.ka; v0 = v.va; k1 = v.kb; v1 = v.vb;
-    if (gsr_radix_sort_pairs(k0, v0, k1, v1, n, v.cnt + VW_CNT_ENTRIES, 0, img_bits, 8, true, v.hist, &in_b, s)) return 1;
-    if (in_b) { std::swap(k0, k1); std::swap(v0, v1); }
-    hipLaunchKernelGGL(k_vw_image_offsets, dim3(gsr_div_up(Cu + 1u, VW_BLOCK)), dim3(VW_BLOCK), 0, s, k0, n, v.cnt, Cu, v.ioff);
+    GsrSort by_img(v.so);
+    if (by_img.sort(n, v.cnt + VW_CNT_ENTRIES, img_bits, true, s)) return 1;
+    hipLaunchKernelGGL(k_vw_image_offsets, dim3(gsr_div_up(Cu + 1u, VW_BLOCK)), dim3(VW_BLOCK), 0, s, by_img.keys, n, v.cnt, Cu, v.ioff);
     const size_t lds = (size_t)Cu * sizeof(double);
     if (lds > 65536) GSR_CHECK(hipFuncSetAttribute((const void*)k_vw_score, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "view_select: LDS row");
     const VwParams q = {theta0, sigma1, sigma2};
-    hipLaunchKernelGGL(k_vw_score, dim3(Cu), dim3(VW_WAVE), lds, s, centres, Cu, point_xyz, n, v.cnt, v.ioff, v0, v.etrack, v.tmap, v.tpi, v.emap, v.eimg, q, (uint32_t)k,
+    hipLaunchKernelGGL(k_vw_score, dim3(Cu), dim3(VW_WAVE), lds, s, centres, Cu, point_xyz, n, v.cnt, v.ioff, by_img.order, v.etrack, v.tmap, v.tpi, v.emap, v.eimg, q, (uint32_t)k,
                        near_ids, near_scores, scores, status_dev);
     return gsr_check_launch(who, s, false);
 }

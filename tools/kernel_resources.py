@@ -10,7 +10,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 PRE = ["-ffp-contract=off"]
 BLEND = ["-ffp-contract=fast", "-fno-slp-vectorize"]
 # the units the Makefile builds with PRE_FLAGS and with BLEND_FLAGS; every other unit gets COMMON alone
-FLAGS = {f"gsr_{u}.hip": PRE for u in ("preprocess", "extra", "binning", "mvloss", "tsdf_sparse", "tsdf_mesh", "unbounded", "mesh_post", "anchor", "densify", "init", "views", "partition")}
+FLAGS = {f"gsr_{u}.hip": PRE for u in ("preprocess", "extra", "binning", "mvloss", "tsdf_sparse", "tsdf_mesh", "unbounded", "mesh_post", "anchor", "densify", "init", "views", "partition", "chamfer", "mesh_simplify")}
 FLAGS.update({"gsr_blend.hip": BLEND, "gsr_blend_sp.hip": BLEND})
 
 
