@@ -190,6 +190,13 @@ FUNCTIONS = [
     ("gsr_mesh_simplify_scratch_bytes", sz, [i64, i64, i32]),
     ("gsr_mesh_simplify_count", cint, [vp, i64, vp, i64, f64, i32, vp, sz, vp, vp]),
     ("gsr_mesh_simplify_emit", cint, [vp, vp, i64, i64, f64, i32, vp, sz, P(u32), vp, vp, vp, vp, vp]),
+    ("gsr_mesh_adjacency_scratch_bytes", sz, [i64, i64]),
+    ("gsr_mesh_adjacency_count", cint, [vp, i64, i64, vp, sz, vp, vp]),
+    ("gsr_mesh_adjacency_emit", cint, [i64, i64, vp, sz, P(u32), vp, vp, vp]),
+    ("gsr_mesh_normals_scratch_bytes", sz, [i64, i64]),
+    ("gsr_mesh_normals", cint, [vp, i64, vp, i64, i32, vp, vp, vp, sz, vp, vp]),
+    ("gsr_mesh_smooth_scratch_bytes", sz, [i64, i64, i32]),
+    ("gsr_mesh_smooth", cint, [vp, vp, i64, vp, i64, i32, i32, f64, f64, i32, vp, vp, vp, sz, vp, vp]),
     ("gsr_unbounded_lattice_points", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, vp, vp, vp]),
     ("gsr_unbounded_lattice_tsdf", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, i32, vp, i32, i32, vp, vp, vp, vp]),
     ("gsr_unbounded_mc_scratch_bytes", sz, [i32, i32, i32]),

@@ -7,6 +7,10 @@ buffer; the cluster areas are added up with double atomics and are the one resul
 `simplify_vertex_clustering` is the step after it: the mesh made smaller by vertex clustering (csrc/gsr_mesh_simplify.hip), the role
 of Open3D's call of that name with semantics of this project's own -- no float atomics, every output bit-reproducible.
 
+`vertex_adjacency`, `filter_smooth_simple` / `_laplacian` / `_taubin` and `compute_triangle_normals` / `compute_vertex_normals` take the voxel-scale
+ripple off such a mesh and give it normals (csrc/gsr_mesh_smooth.hip), again with semantics of this project's own: every sum in a
+stated order, float64 state, no float atomics.
+
 There is no CPU path: a mesh that is not on a HIP device raises, like ScalableTSDFVolume."""
 import ctypes as C
 import math
@@ -175,6 +179,129 @@ def simplify_vertex_clustering(mesh, voxel_size, contraction="average", return_m
     nv, nc, tris, vmap, _ = _simplify(mesh, voxel_size, contraction, return_map)
     out = TriangleMesh(nv, nc, tris)
     return (out, vmap) if return_map else out
+
+
+SMOOTH_SIMPLE, SMOOTH_LAPLACIAN, SMOOTH_TAUBIN = 0, 1, 2    # GSR_SMOOTH_*
+SCOPES = {"all": 0, "vertex": 1}                           # GSR_SMOOTH_SCOPE_*
+
+
+def _limits(T, V):
+    return RuntimeError(f"mesh: {T} triangles / {V} vertices: V and 3T must stay below 2^31; process the mesh in parts")
+
+
+def _raise_smooth_status(status):
+    if status & ERR_NONFINITE:
+        raise RuntimeError("mesh: a vertex has a non-finite component (NaN or inf)")
+    _raise_status(status)
+
+
+def vertex_adjacency(mesh):
+    """-> (start int32 [V + 1], neighbours int32 [E]) as device tensors: the vertex -> vertex adjacency of the index buffer as a CSR.
+    N(i) = neighbours[start[i] : start[i + 1]] is the set of j != i that share at least one triangle with i, distinct and ascending; a triangle with
+    two equal indices adds no self-loop and still connects its two distinct vertices (include/gsrast.h, "mesh smoothing and normals").
+    Raises RuntimeError for a triangle index outside [0, V).  Exactly ONE host read-back per call: the record {status, E} between the counting and
+    the emitting pass."""
+    v, _, t = _arrays(mesh)
+    T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
+    nbytes = int(lib().gsr_mesh_adjacency_scratch_bytes(T, V))
+    if nbytes == 0:
+        raise _limits(T, V)
+    work = scratch(nbytes, dev)
+    record = torch.empty(8, dtype=torch.int32, device=dev)
+    call("gsr_mesh_adjacency_count", dev, t if T else None, T, V, work, nbytes, record)
+    rec = [x & 0xFFFFFFFF for x in record.tolist()]                       # the host read-back
+    _raise_status(rec[0])
+    start = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    neighbours = torch.empty(rec[1], dtype=torch.int32, device=dev)
+    call("gsr_mesh_adjacency_emit", dev, T, V, work, nbytes, (C.c_uint32 * 8)(*rec), start, neighbours if rec[1] else None)
+    return start, neighbours
+
+
+def _normals(mesh, normalized, want_triangle, want_vertex):
+    """One call, one read-back (the status word) -> (triangle_normals or None, vertex_normals or None)."""
+    v, _, t = _arrays(mesh)
+    T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
+    nbytes = int(lib().gsr_mesh_normals_scratch_bytes(T, V))
+    if nbytes == 0:
+        raise _limits(T, V)
+    work = scratch(nbytes if want_vertex else 1, dev)
+    tn = torch.empty((T, 3), dtype=torch.float32, device=dev) if want_triangle else None
+    vn = torch.empty((V, 3), dtype=torch.float32, device=dev) if want_vertex else None
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    call("gsr_mesh_normals", dev, v if V else None, V, t if T else None, T, 1 if normalized else 0, tn, vn, work, nbytes if want_vertex else 0, status)
+    _raise_status(status.tolist()[0] & 0xFFFFFFFF)                        # the host read-back
+    return tn, vn
+
+
+def compute_triangle_normals(mesh, normalized=True):
+    """-> triangle_normals float32 [T,3] on the mesh's device: n = (v1 - v0) x (v2 - v0) in float64 from the float32 vertices, divided by its length
+    when `normalized` -- (0, 0, 1) where that length is 0 or not finite -- and rounded to float32 once.  The role of Open3D's
+    `compute_triangle_normals`; the semantics are this project's own (include/gsrast.h), parity with Open3D unpinned.
+    Exactly ONE host read-back per call: the status word."""
+    return _normals(mesh, normalized, True, False)[0]
+
+
+def compute_vertex_normals(mesh, normalized=True):
+    """-> vertex_normals float32 [V,3] on the mesh's device: per vertex the float64 sum of the UNNORMALISED normals of the triangles that reference
+    it (area weighting), added in ascending corner index 3 t + k, then normalised like a triangle normal (or left as the sum) and rounded to float32
+    once.  A vertex no triangle references gets (0, 0, 1) when normalised and (0, 0, 0) when not.  No float atomics: two runs give the same bits.
+    The role of Open3D's `compute_vertex_normals`, parity unpinned.  Exactly ONE host read-back per call: the status word."""
+    return _normals(mesh, normalized, False, True)[1]
+
+
+def _smooth(mesh, kind, number_of_iterations, lam, mu, filter_scope):
+    """The argument checks, one call, one read-back (the status word) -> a new TriangleMesh."""
+    from .tsdf import TriangleMesh
+    n = number_of_iterations
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n > 0x3FFFFFFF:
+        raise ValueError(f"number_of_iterations must be a non-negative integer but found {n!r}")
+    if filter_scope not in SCOPES:
+        raise ValueError(f"filter_scope must be one of {sorted(SCOPES)} but found {filter_scope!r}")
+    for name, x in (("lambda_filter", lam), ("mu", mu)):
+        if not math.isfinite(float(x)):
+            raise ValueError(f"{name} must be a finite number but found {x}")
+    v, c, t = _arrays(mesh)
+    T, V, dev = int(t.shape[0]), int(v.shape[0]), t.device
+    nbytes = int(lib().gsr_mesh_smooth_scratch_bytes(T, V, SCOPES[filter_scope]))
+    if nbytes == 0:
+        raise _limits(T, V)
+    work = scratch(nbytes, dev)
+    nv, nc = torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((V, 3), dtype=torch.float32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    call("gsr_mesh_smooth", dev, v if V else None, c if V else None, V, t if T else None, T, kind, int(n), float(lam), float(mu), SCOPES[filter_scope],
+         nv if V else None, nc if V else None, work, nbytes, status)
+    tris = t.clone()
+    _raise_smooth_status(status.tolist()[0] & 0xFFFFFFFF)                 # the host read-back
+    return TriangleMesh(nv, nc, tris)
+
+
+def filter_smooth_simple(mesh, number_of_iterations=1, filter_scope="all"):
+    """-> a NEW mesh: per iteration every vertex becomes the mean of itself and its neighbours, q_i = (p_i + sum p_j) / (|N(i)| + 1).  See
+    filter_smooth_taubin for what all three filters share."""
+    return _smooth(mesh, SMOOTH_SIMPLE, number_of_iterations, 0.0, 0.0, filter_scope)
+
+
+def filter_smooth_laplacian(mesh, number_of_iterations=1, lambda_filter=0.5, filter_scope="all"):
+    """-> a NEW mesh: per iteration q_i = p_i + lambda * (sum w_ij p_j / sum w_ij - p_i) with w_ij = 1 / (|p_i - p_j| + 1e-12) on the positions of
+    the iteration's input.  It shrinks the mesh; filter_smooth_taubin does not.  See there for what all three filters share."""
+    return _smooth(mesh, SMOOTH_LAPLACIAN, number_of_iterations, lambda_filter, 0.0, filter_scope)
+
+
+def filter_smooth_taubin(mesh, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, filter_scope="all"):
+    """-> a NEW mesh: per iteration a Laplacian step with lambda_filter, then one with mu (negative: it undoes the shrinkage of the first).
+    The role of Open3D's `filter_smooth_taubin` / `_laplacian` / `_simple`; the semantics are this project's own (include/gsrast.h, "mesh smoothing
+    and normals"), parity with Open3D unpinned.  What the three filters share:
+      * N(i), the vertices that share a triangle with i, is walked in ascending order and every sum is added one term after another in float64;
+        the state stays float64 from the first iteration to the last and is rounded to float32 once.  No float atomics: two runs give the same bits.
+      * filter_scope="all" filters positions and colours (the colours with the positions' weights; they are the only further channel that is
+        filtered), "vertex" positions only: the colours are copied bit for bit.
+      * a vertex without neighbours stays where it is -- a departure from the model, which divides 0 by 0 there.
+      * number_of_iterations=0 returns a copy, bit for bit.  The new mesh has a copy of the input's triangles and NO normals: compute_vertex_normals
+        is one call.
+    Raises ValueError before any launch for a negative or non-integer number_of_iterations, a non-finite lambda_filter / mu or an unknown
+    filter_scope; RuntimeError for a triangle index outside [0, V), a non-finite vertex, a host mesh or a mesh past V, 3T < 2^31.
+    Exactly ONE host read-back per call, whatever the number of iterations: the status word, behind all the steps."""
+    return _smooth(mesh, SMOOTH_TAUBIN, number_of_iterations, lambda_filter, mu, filter_scope)
 
 
 def as_remove_mask(mask, n, device):

@@ -155,21 +155,31 @@ def load_anchors(path, device="cpu"):
 def write_triangle_mesh(path, mesh):
     """The mesh file `o3d.io.write_triangle_mesh` leaves for the reference (extract_mesh.py:130-135): binary little-endian PLY, element `vertex` with
     x, y, z float and red, green, blue uchar, element `face` with `vertex_indices` as list uchar int.  mesh: anything with vertices [V,3],
-    vertex_colors [V,3] in [0,1] and triangles [T,3] (gsrast.tsdf.TriangleMesh, on any device)."""
+    vertex_colors [V,3] in [0,1] and triangles [T,3] (gsrast.tsdf.TriangleMesh, on any device).  A mesh that has vertex normals
+    (`vertex_normals` [V,3], not None) gets nx, ny, nz float between z and red, where Open3D writes them; one without gives the same bytes as ever."""
     v = np.asarray(mesh.vertices.detach().cpu(), dtype="<f4").reshape(-1, 3)
     c = np.asarray(mesh.vertex_colors.detach().cpu(), dtype=np.float64).reshape(-1, 3)
     t = np.asarray(mesh.triangles.detach().cpu(), dtype="<i4").reshape(-1, 3)
     if c.shape != v.shape:
         raise ValueError(f"gsrast.ply: {c.shape[0]} colours for {v.shape[0]} vertices")
-    vert = np.empty(v.shape[0], dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    n = getattr(mesh, "vertex_normals", None)
+    if n is not None:
+        n = np.asarray(n.detach().cpu(), dtype="<f4").reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"gsrast.ply: {n.shape[0]} normals for {v.shape[0]} vertices")
+    normal_fields = [] if n is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vert = np.empty(v.shape[0], dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + normal_fields + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     c8 = np.clip(np.rint(np.nan_to_num(c) * 255.0), 0, 255).astype(np.uint8)
     vert["red"], vert["green"], vert["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
     face = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     face["n"] = 3
     face["i"] = t
-    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z",
-            "property uchar red", "property uchar green", "property uchar blue", f"element face {t.shape[0]}",
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z"] + \
+           [f"property float {name}" for name, _ in normal_fields] + \
+           ["property uchar red", "property uchar green", "property uchar blue", f"element face {t.shape[0]}",
             "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode("ascii"))
@@ -178,8 +188,9 @@ def write_triangle_mesh(path, mesh):
 
 
 def read_triangle_mesh(path, device="cpu"):
-    """-> gsrast.tsdf.TriangleMesh of a binary little-endian PLY file with a `vertex` element (x, y, z and, optionally, red, green, blue; further
-    scalar properties are skipped) followed by a `face` element whose only property is a list of three indices per face."""
+    """-> gsrast.tsdf.TriangleMesh of a binary little-endian PLY file with a `vertex` element (x, y, z and, optionally, red, green, blue and
+    nx, ny, nz; further scalar properties are skipped) followed by a `face` element whose only property is a list of three indices per face.
+    vertex_normals is filled when the file has all of nx, ny, nz and stays None otherwise."""
     from .tsdf import TriangleMesh
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
@@ -218,4 +229,7 @@ def read_triangle_mesh(path, device="cpu"):
         col = np.zeros((nv, 3), np.float32)
     tri = face["i"].astype(np.int32).reshape(nf, 3)
     t = lambda a, dt: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=device)
-    return TriangleMesh(t(xyz, torch.float32), t(col, torch.float32), t(tri, torch.int32))
+    normals = None
+    if all(k in vdt.names for k in ("nx", "ny", "nz")):
+        normals = t(np.stack([vert["nx"], vert["ny"], vert["nz"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32), torch.float32)
+    return TriangleMesh(t(xyz, torch.float32), t(col, torch.float32), t(tri, torch.int32), normals)

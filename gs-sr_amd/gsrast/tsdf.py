@@ -98,19 +98,32 @@ def brick_to_xmajor(planes):
 class TriangleMesh:
     """What `ScalableTSDFVolume.extract_triangle_mesh()` returns -- the three arrays of Open3D's `TriangleMesh` the reference goes on to use
     (extract_mesh.py:130-135 writes them to a PLY file): vertices [V,3] float32, vertex_colors [V,3] float32 in [0,1], triangles [T,3] int32,
-    on the volume's device."""
+    on the volume's device.  vertex_normals [V,3] and triangle_normals [T,3] (float32) are optional and None until compute_vertex_normals() /
+    compute_triangle_normals() fill them; whatever changes the vertices or the triangles -- the in-place filters below, and every function that
+    returns a new mesh -- leaves them None: recomputing them is one call."""
 
-    def __init__(self, vertices, vertex_colors, triangles):
+    def __init__(self, vertices, vertex_colors, triangles, vertex_normals=None, triangle_normals=None):
         self.vertices, self.vertex_colors, self.triangles = vertices, vertex_colors, triangles
+        self.vertex_normals, self.triangle_normals = vertex_normals, triangle_normals
+
+    def _map(self, f):
+        g = lambda x: None if x is None else f(x)
+        return TriangleMesh(f(self.vertices), f(self.vertex_colors), f(self.triangles), g(self.vertex_normals), g(self.triangle_normals))
 
     def cpu(self):
-        return TriangleMesh(self.vertices.cpu(), self.vertex_colors.cpu(), self.triangles.cpu())
+        return self._map(lambda x: x.cpu())
 
     def clone(self):
-        return TriangleMesh(self.vertices.clone(), self.vertex_colors.clone(), self.triangles.clone())
+        return self._map(lambda x: x.clone())
 
     def __deepcopy__(self, memo):
         return self.clone()
+
+    def has_vertex_normals(self):
+        return self.vertex_normals is not None and int(self.vertex_normals.shape[0]) > 0
+
+    def has_triangle_normals(self):
+        return self.triangle_normals is not None and int(self.triangle_normals.shape[0]) > 0
 
     # The four Open3D calls of the reference's post_process_mesh (gssr/utils/mesh_utils.py:33-45), under their names, so that its body runs against
     # this class as it stands; gsrast.mesh.post_process_mesh is the same filter as one call with one host read-back.  No CPU path: a host mesh raises.
@@ -123,6 +136,7 @@ class TriangleMesh:
     def _filter_(self, **kw):
         from . import mesh as _m
         self.vertices, self.vertex_colors, self.triangles, _ = _m._filter(self, **kw)
+        self.vertex_normals = self.triangle_normals = None                    # they belonged to the mesh before the filter
         return self
 
     def remove_triangles_by_mask(self, mask):
@@ -146,6 +160,30 @@ class TriangleMesh:
         hands out the vertex map).  contraction: "average" or "quadric"."""
         from . import mesh as _m
         return _m.simplify_vertex_clustering(self, voxel_size, contraction)
+
+    # Normals and smoothing (gsrast.mesh; DESIGN.md 4.15) under Open3D's names: the compute_* calls work in place and return self, the filters
+    # return a NEW mesh without normals, as the model's do.
+    def compute_triangle_normals(self, normalized=True):
+        from . import mesh as _m
+        self.triangle_normals = _m.compute_triangle_normals(self, normalized)
+        return self
+
+    def compute_vertex_normals(self, normalized=True):
+        from . import mesh as _m
+        self.vertex_normals = _m.compute_vertex_normals(self, normalized)
+        return self
+
+    def filter_smooth_simple(self, number_of_iterations=1, filter_scope="all"):
+        from . import mesh as _m
+        return _m.filter_smooth_simple(self, number_of_iterations, filter_scope)
+
+    def filter_smooth_laplacian(self, number_of_iterations=1, lambda_filter=0.5, filter_scope="all"):
+        from . import mesh as _m
+        return _m.filter_smooth_laplacian(self, number_of_iterations, lambda_filter, filter_scope)
+
+    def filter_smooth_taubin(self, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, filter_scope="all"):
+        from . import mesh as _m
+        return _m.filter_smooth_taubin(self, number_of_iterations, lambda_filter, mu, filter_scope)
 
     def __repr__(self):
         return f"TriangleMesh({int(self.vertices.shape[0])} vertices, {int(self.triangles.shape[0])} triangles, {self.vertices.device})"

@@ -659,6 +659,59 @@ int gsr_mesh_simplify_count(const float* vertices /*[V,3]*/, int64_t n_vertices,
 int gsr_mesh_simplify_emit(const float* vertices, const float* vertex_colors /*[V,3]*/, int64_t n_vertices, int64_t n_triangles, double voxel_size,
                            int32_t contraction, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/, float* vertices_out,
                            float* vertex_colors_out, int32_t* triangles_out, int32_t* vertex_map_out /*[V] or NULL*/, void* stream);
+/* ---- mesh smoothing and normals (no ABI bump: additions only).
+ * The role of Open3D's filter_smooth_simple / filter_smooth_laplacian / filter_smooth_taubin, compute_triangle_normals and compute_vertex_normals
+ * on the mesh post_process_mesh and the simplification leave.  Open3D 0.18's published sources are the model (area-weighted vertex normals,
+ * inverse-distance Laplacian weights, the (0, 0, 1) fallback) but Open3D is not part of the reference tree and PARITY IS UNPINNED: the semantics
+ * below are this project's own, stated so that every result is deterministic (no float atomics: two runs give the same bits), and restated operation
+ * by operation in tests/smooth_truth.py.  Mesh: vertices [V,3] float32, vertex_colors [V,3] float32, triangles [T,3] int32; V < 2^31 and 3T < 2^31,
+ * every *_scratch_bytes function below returns 0 beyond that (and for an unknown scope).
+ *   1. adjacency: N(i) = the set of j != i that share at least one triangle with i, distinct and ascending.  A triangle with two equal indices
+ *      adds no self-loop and still connects its two distinct vertices.  A triangle index outside [0, V) sets GSR_MESH_ERR_INDEX; nothing is
+ *      dereferenced through it and its triangle connects nothing.  The result is a CSR: start int32 [V + 1], neighbours int32 [E],
+ *      N(i) = neighbours[start[i] .. start[i + 1]).
+ *   2. triangle normal: n_t = (v1 - v0) x (v2 - v0), the float32 inputs widened to float64 and every operation in float64, rounded on its own:
+ *      e1 = v1 - v0, e2 = v2 - v0, n_t = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x).  normalized: n_t / L per component with
+ *      L = sqrt((nx nx + ny ny) + nz nz); where L is 0 or not finite the normal is (0, 0, 1).  Rounded to float32 once.
+ *   3. vertex normal: the float64 sum, starting from 0, of the UNNORMALISED n_t over the corners that reference the vertex, added in ascending
+ *      corner index 3 t + k (area weighting; a triangle that names a vertex twice adds twice); then normalised by the rule of 2, or left as the
+ *      sum with normalized = 0; rounded to float32 once.  An unreferenced vertex gets (0, 0, 1) when normalised and (0, 0, 0) when not.
+ *   4. smoothing: the state p (positions; with GSR_SMOOTH_SCOPE_ALL also the colours -- the only further channel that is filtered, normals are
+ *      not) is held in float64 from the first step to the last and rounded to float32 once at the end.  Every sum runs over N(i) in ascending
+ *      order, one addition after another.  One step, from p to q:
+ *        GSR_SMOOTH_SIMPLE     q_i = (p_i + sum_j p_j) / (double)(|N(i)| + 1), the sum starting from p_i.
+ *        GSR_SMOOTH_LAPLACIAN  d = p_i - p_j on the positions of the step's input, w_ij = 1.0 / (sqrt((dx dx + dy dy) + dz dz) + 1e-12);
+ *                              W = sum w_ij and s = sum w_ij * p_j per channel, both starting from 0; q_i = p_i + lambda * (s / W - p_i).  The colours
+ *                              use the same w.  N(i) empty: q_i = p_i -- a DEPARTURE from the model, which divides 0 by 0 there.
+ *        GSR_SMOOTH_TAUBIN     one iteration = a Laplacian step with lambda, then one with mu (the model's defaults: 0.5 and -0.53).
+ *      iterations = 0 copies vertices and colours bit for bit and looks at nothing.  GSR_SMOOTH_SCOPE_VERTEX copies the colours bit for bit.  A
+ *      non-finite vertex component sets GSR_MESH_ERR_NONFINITE, an index out of range GSR_MESH_ERR_INDEX; with a status the results are to be
+ *      discarded.  The triangles are not touched: the smoothed mesh has the input's.
+ * gsr_mesh_adjacency_count: everything up to the count; record_dev [8 words, 2 used] = {status, E}.  The caller reads the record (its one host
+ *   synchronisation), allocates, and calls gsr_mesh_adjacency_emit with the HOST copy of the record and the UNMODIFIED scratch
+ *   (>= gsr_mesh_adjacency_scratch_bytes(T, V), caller-owned): it refuses a non-zero status and an E beyond 2^31 - 1 and writes start_out [V + 1] and
+ *   neighbours_out [E].
+ * gsr_mesh_normals: either output may be NULL; scratch (>= gsr_mesh_normals_scratch_bytes(T, V)) is needed for the vertex normals only;
+ *   status_dev [1].
+ * gsr_mesh_smooth: builds the adjacency in scratch (>= gsr_mesh_smooth_scratch_bytes(T, V, scope)) and enqueues every step behind it; the number
+ *   of launches is a constant plus a constant times `iterations`, and nothing synchronises.  status_dev [2] = {status, E}.  lambda is ignored by
+ *   GSR_SMOOTH_SIMPLE, mu by everything but GSR_SMOOTH_TAUBIN.  The outputs must not alias the inputs.
+ * Inputs are only read.  Keeping the state in float32 between the steps would halve the gathered bytes and is not offered. */
+enum { GSR_SMOOTH_SIMPLE = 0, GSR_SMOOTH_LAPLACIAN = 1, GSR_SMOOTH_TAUBIN = 2 };
+enum { GSR_SMOOTH_SCOPE_ALL = 0, GSR_SMOOTH_SCOPE_VERTEX = 1 };
+size_t gsr_mesh_adjacency_scratch_bytes(int64_t n_triangles, int64_t n_vertices);
+int gsr_mesh_adjacency_count(const int32_t* triangles /*[T,3]*/, int64_t n_triangles, int64_t n_vertices, void* scratch, size_t scratch_bytes,
+                             uint32_t* record_dev /*[8]*/, void* stream);
+int gsr_mesh_adjacency_emit(int64_t n_triangles, int64_t n_vertices, const void* scratch, size_t scratch_bytes, const uint32_t* record /*[8] host*/,
+                            int32_t* start_out /*[V+1]*/, int32_t* neighbours_out /*[E]*/, void* stream);
+size_t gsr_mesh_normals_scratch_bytes(int64_t n_triangles, int64_t n_vertices);
+int gsr_mesh_normals(const float* vertices /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles, int32_t normalized,
+                     float* triangle_normals_out /*[T,3] or NULL*/, float* vertex_normals_out /*[V,3] or NULL*/, void* scratch, size_t scratch_bytes,
+                     uint32_t* status_dev /*[1]*/, void* stream);
+size_t gsr_mesh_smooth_scratch_bytes(int64_t n_triangles, int64_t n_vertices, int32_t scope);
+int gsr_mesh_smooth(const float* vertices, const float* vertex_colors /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles,
+                    int32_t filter, int32_t iterations, double lambda, double mu, int32_t scope, float* vertices_out, float* vertex_colors_out /*[V,3]*/,
+                    void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[2]*/, void* stream);
 /* ---- the mesh of an unbounded scene (no ABI bump: additions only).
  * GaussianExtractor.extract_mesh_unbounded (gssr/utils/mesh_utils.py:181-277) over marching_cubes_with_contraction (gssr/utils/mcube_utils.py:17-95).
  * THE LATTICE.  Samples live in contracted coordinates on a dense lattice with ascending float32 axes xs[nx], ys[ny], zs[nz] (device arrays), flat
