@@ -102,6 +102,11 @@ def cell_order_keys(a, origin, cell):
 # over, and a third workgroup that holds one entry
 @pytest.mark.parametrize("N,k,F", [(300000, 10, 32), (77777, 3, 5), (341, 2, 5), (512, 1, 5), (205, 4, 5), (683, 2, 5)])
 def test_anchor_growing_equals_restatement(N, k, F):
+    growing_equals_restatement(N, k, F)
+
+
+def growing_equals_restatement(N, k, F):
+    """-> (the scene, the levels' counts); tests/test_gpu_sort_paths.py runs it on both sides of the sort's digit-major switch."""
     from gsrast import anchors
     vs = 0.01
     s = random_scene(N, k, F, seed=N % 97, cell=vs * 4)
@@ -119,6 +124,7 @@ def test_anchor_growing_equals_restatement(N, k, F):
         key = cell_order_keys(got["anchor"][p:p + c].cpu(), (0.0, 0.0, 0.0), vs * (16 // 4 ** i))
         assert bool((key[1:] > key[:-1]).all()), i
         p += c
+    return s, counts
 
 
 @pytest.mark.parametrize("N,k,F", [(300000, 10, 32), (77777, 3, 5)])

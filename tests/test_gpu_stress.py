@@ -1,10 +1,16 @@
 """GPU stress / robustness tests: extreme instance counts, screen-filling splats, many tiles, stream usage, debug mode."""
+import functools
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
 import scenes
+import sort_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -229,17 +235,8 @@ def test_dense_tile_lists_backward_through_the_chunk_halving_path(variant):
         assert np.linalg.norm(x - y) <= 1e-3 * np.linalg.norm(y) + 1e-12, (variant, a, np.linalg.norm(x - y) / np.linalg.norm(y))
 
 
-@pytest.mark.parametrize("P", [1, 63, 1023, 1024, 1025, 16384, 16385, 17 * 1024 + 5, 786432, 786433, 787456 + 7])
-def test_sort_block_and_group_boundaries(P):
-    """The radix passes keep one histogram per block of 1024 keys and one per group of 16 blocks; beyond 48 groups the sort switches to
-    the digit-major matrix + row scan.  Counts on both sides of every boundary: the depth order and the per-tile lists stay exact
-    (stable: equal depths keep index order)."""
-    hr = _hr()
-    W, H = 96, 64
-    sc = scenes.make_scene("ewa", P, W, H, seed=P % 97, sigma_px=0.8)
-    if P > 4:
-        sc["means3D"][P // 3] = sc["means3D"][P // 3 - 1]            # a depth tie whose order only stability decides
-    st = hr.run_raw("ewa", sc)
+def _sort_checks(st, sc, P):
+    """The size-independent checks of the two sorts: every instance once, keys non-decreasing, (depth bits, id) order inside a tile, ranges = key counts."""
     assert st["R"] == int(st["tiles_touched"].sum())
     tk, pl = st["tile_keys"].astype(np.int64)[: st["R"]], st["point_list"].astype(np.int64)[: st["R"]]
     assert np.all(np.diff(tk) >= 0)
@@ -251,3 +248,91 @@ def test_sort_block_and_group_boundaries(P):
     assert np.all((db[a] < db[b]) | ((db[a] == db[b]) & (a < b)))
     counts = np.bincount(tk, minlength=st["ranges"].shape[0])
     assert np.array_equal(st["ranges"][:, 1] - st["ranges"][:, 0], counts)
+    return counts
+
+
+def _run_raw_exact(variant, sc):
+    """run_raw with the arena sized from the exact instance count (no capacity hint of an earlier call on this image size): the tile sort's n is R."""
+    from gsrast import rasterize as rz
+    hr = _hr()
+    rz._R_HINT.pop((torch.cuda.current_device(), hr.VID[variant], int(sc["W"]), int(sc["H"])), None)
+    return hr.run_raw(variant, sc)
+
+
+def _depth_order_switch():
+    e = os.environ.get("GSR_DEPTH_ORDER", "")
+    return "global" if e[:1] == "g" else ("tile" if e[:1] == "t" else "auto")
+
+
+@functools.lru_cache(maxsize=None)
+def _smallest_counts_in_a_global_order_process():
+    """P = 1 and P = 63 take the per-tile depth order on any image (gsr_depth_order_static_rule), and GSR_DEPTH_ORDER is read once per process: both
+    cases run in ONE child process with GSR_DEPTH_ORDER=global, the way test_gpu_parity.py::test_kept_switches_keep_the_results runs its sets."""
+    me = os.path.abspath(__file__)
+    ids = [f"{me}::test_sort_block_and_group_boundaries[{P}]" for P in SORT_SIZES if "depth" not in sort_cases.forward_sorts("ewa", P, 1)]
+    r = subprocess.run([sys.executable, "-m", "pytest", *ids, "-v", "-m", "gpu", "-p", "no:cacheprovider"], env=dict(os.environ, GSR_DEPTH_ORDER="global"),
+                       capture_output=True, text=True, timeout=180, cwd=os.path.dirname(os.path.dirname(me)))
+    return r.returncode, r.stdout[-3000:] + r.stderr[-1000:]
+
+
+_SORT_LIMITS = sort_cases.limits()
+SORT_SIZES = sorted([1, 63, _SORT_LIMITS["block"] - 1, 17 * _SORT_LIMITS["block"] + 5]
+                    + [n for name in ("block", "group", "row_chunk", "digit_major") for n in sort_cases.around(_SORT_LIMITS[name])])
+
+
+@pytest.mark.parametrize("P", SORT_SIZES)
+def test_sort_block_and_group_boundaries(P):
+    """The depth sort of the P gaussians (four 8-bit passes) keeps one histogram per block of 1024 keys and one per group of 16 blocks, fetches the
+    group rows 16 at a time, and beyond GSR_SORT_MAX_GROUPS groups switches to the digit-major matrix + row scan.  Counts on both sides of every one
+    of these limits (tests/sort_cases.py reads them from the sources), plus 1, 63, a block less one and a partial eighteenth block: the depth order and the per-tile lists stay exact (stable:
+    equal depths keep index order).
+    The image is ONE tile, 16 x 16: the static rule then sends every P above its per-tile factor to the global order, so the depth sort this test is
+    named after does run -- asserted first.  P = 1 and 63 are below the factor on any image and run in a child process with GSR_DEPTH_ORDER=global.
+    The tile sort that follows has one tile bit: one pass over the R < P instances, in 1024-key blocks -- at the digit-major switch R stays below
+    big_from0, the near side of the 4096-key blocks (test_tile_sort_with_4096_key_blocks has the far side)."""
+    W, H = 16, 16
+    switch = _depth_order_switch()
+    if "depth" not in sort_cases.forward_sorts("ewa", P, 1, depth_order=switch):
+        assert switch == "auto" and P <= 155
+        code, out = _smallest_counts_in_a_global_order_process()
+        assert code == 0 and f"[{P}] PASSED" in out, out
+        return
+    assert sort_cases.forward_sorts("ewa", P, 1, depth_order=switch) == ("depth", "tile") and len(sort_cases.passes(32)) == 4
+    path = sort_cases.path(P)
+    near = {_SORT_LIMITS[name]: name for name in ("block", "group", "row_chunk", "digit_major")}
+    if P in near:                                                        # the last count on the near side
+        assert path == sort_cases.path(P - 1 if P > 1 else 1) and path != sort_cases.path(P + 1), near[P]
+    elif P - 1 in near:                                                  # the first on the far side
+        assert path != sort_cases.path(P - 1), near[P - 1]
+        assert path.digit_major == (near[P - 1] == "digit_major") and (path.row_chunks > 1) == (near[P - 1] == "row_chunk")
+    else:                                                                # 1, 63, a block less one, two groups and a partial block
+        assert path.blocks in (1, 18) and not path.digit_major
+    sc = scenes.make_scene("ewa", P, W, H, seed=P % 97, sigma_px=0.8)
+    if P > 4:
+        sc["means3D"][P // 3] = sc["means3D"][P // 3 - 1]            # a depth tie whose order only stability decides
+    st = _run_raw_exact("ewa", sc)
+    counts = _sort_checks(st, sc, P)
+    assert counts.shape == (1,) and sort_cases.passes(sort_cases.tile_bits(1)) == [1]
+    assert P < 64 or st["R"] > P // 2
+    assert st["R"] < _SORT_LIMITS["big_from0"] and not sort_cases.tile_sort_big_blocks(st["R"]) and not sort_cases.path(st["R"]).digit_major
+
+
+@pytest.mark.parametrize("name,P,sigma_px", [pytest.param("big_blocks", 500000, 4.0, id="big_blocks"),
+                                             pytest.param("big_blocks_digit_major", 1500000, 4.5, id="big_blocks_digit_major")])
+def test_tile_sort_with_4096_key_blocks(name, P, sigma_px):
+    """The forward's tile sort in the global depth order on a 400-tile image: 9 tile bits, two balanced passes (5, 4), no list beyond a few tens of
+    thousands.  From big_from0 instances on the sort takes 4096-key blocks; above GSR_SORT_MAX_GROUPS groups of them, 6 291 456 instances, the
+    digit-major form as well.  The arena is sized from the exact count, so the sort's n is R itself.  Size-independent checks, no CPU oracle."""
+    W = H = 320
+    T = (W // 16) * (H // 16)
+    assert sort_cases.forward_sorts("ewa", P, T) == ("depth", "tile") and sort_cases.passes(sort_cases.tile_bits(T)) == [5, 4]
+    sc = scenes.make_scene("ewa", P, W, H, seed=5, sigma_px=sigma_px)
+    st = _run_raw_exact("ewa", sc)
+    R = st["R"]
+    print(f"{name}: R = {R}")
+    lo, hi = (_SORT_LIMITS["big_from0"], _SORT_LIMITS["digit_major_big"]) if name == "big_blocks" else (_SORT_LIMITS["digit_major_big"] + 1, 1 << 31)
+    assert lo <= R <= hi, (R, lo, hi)
+    big = sort_cases.path(R, big_blocks=True)
+    assert sort_cases.tile_sort_big_blocks(R) and big.digit_major == (name != "big_blocks") and big.groups > 1
+    counts = _sort_checks(st, sc, P)
+    assert counts.shape == (T,) and counts.max() < 60000

@@ -217,6 +217,21 @@ def test_observation_counts_around_the_sort_block(n_obs):
     check(sc, score, 5)
 
 
+@pytest.mark.parametrize("C", [256, 257])
+def test_image_counts_around_one_digit_of_the_image_sort(C):
+    """The (id, image) entries are sorted by image on img_bits = 8 bits for 256 images -- one pass, the result in the other pair of buffers -- and
+    on 9 bits for 257: two balanced passes (5, 4), the result back in the first pair (GsrSort::advance).  More than two sort blocks of entries, their
+    count on the device and below the capacity (the observations, -1 included)."""
+    import sort_cases
+    sc, score = scene(C, 400, 10, 5)
+    imgs = rvs.images(sc["obs_offsets"], sc["obs_ids"])
+    entries = sum(len(np.unique(a[a != -1])) for a in imgs)
+    assert 2 * sort_cases.limits()["block"] < entries < len(sc["obs_ids"]) and sort_cases.path(len(sc["obs_ids"])).blocks > 2
+    widths = sort_cases.passes(sort_cases.tile_bits(C))                      # img_bits is the same smallest b >= 1 with 2^b >= C
+    assert widths == ([8] if C == 256 else [5, 4]) and sort_cases.result_swapped(sum(widths)) == (C == 256)
+    check(sc, score, 5)
+
+
 def test_ids_beyond_32_bits():
     """Ids up to 2^39, among them ids that differ in the high word only: the sort's high-word passes run, and are needed."""
     sc, score = scene(9, 50, 20, 5, wide=True)
