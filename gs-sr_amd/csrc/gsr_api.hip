@@ -146,6 +146,8 @@ GeomView gsr_carve_geom(int variant, int P, void* base)
     g.hist = take<uint32_t>(p, gsr_sort_hist_words(nblk, 256));   // 256-bin digits
     g.scan_tmp = take<uint32_t>(p, gsr_div_up((uint32_t)n, 256) + 64);       // block sums of the prefix: 256-gaussian blocks when the preprocess writes them
     g.counters = take<uint32_t>(p, 64);
+    g.tw_z = nullptr;
+    if (variant == GSR_SURFEL) g.tw_z = take<float>(p, n);      // behind everything else: the other arrays keep their offsets
     g.bytes = (size_t)(p - reinterpret_cast<char*>(base));
     return g;
 }
@@ -617,6 +619,10 @@ extern "C" int gsr_backward_ex(const gsr_cfg* cfg, const gsr_inputs* in, const i
     const size_t need = gsr_backward_scratch_bytes(cfg->variant, cfg->P);
     if (scratch_bytes < need) { gsr_set_error("backward scratch too small: %zu < %zu", scratch_bytes, need); return 1; }
     if (cfg->variant == GSR_PLANE && cfg->render_geo && !og->all_map_pixels) { gsr_set_error("PLANE backward needs all_map_pixels"); return 1; }
+    // the gradients every call writes; dL_dcov3D (SURFEL: dL_dtransMat) may be null = not wanted, as may dL_dsh, dL_dmeans2D_abs and dL_dall_map
+    if (!ig || !ig->dL_dmeans3D || !ig->dL_dmeans2D || !ig->dL_dcolors || !ig->dL_dopacity || !ig->dL_dscales || !ig->dL_drotations) {
+        gsr_set_error("backward: dL_dmeans3D/dL_dmeans2D/dL_dcolors/dL_dopacity/dL_dscales/dL_drotations must be provided"); return 1;
+    }
     Arenas a;      // the sizes of the forward's arenas are not checked again
     if (carve_arenas(cfg, const_cast<void*>(geom), GSR_UNCHECKED, const_cast<void*>(binning), binning_bytes, const_cast<void*>(img), GSR_UNCHECKED, 0, a)) return 1;
     const GeomView& g = a.g;
@@ -661,6 +667,7 @@ extern "C" int gsr_debug_read(const gsr_cfg* cfg, int32_t field, const void* geo
     const void* src = nullptr; size_t bytes = 0;
     switch (field) {
     case GSR_DBG_TILES_TOUCHED: { GeomView g = gsr_carve_geom(cfg->variant, cfg->P, const_cast<void*>(geom)); src = g.tiles_touched; bytes = (size_t)cfg->P * 4; break; }
+    case GSR_DBG_REC: { GeomView g = gsr_carve_geom(cfg->variant, cfg->P, const_cast<void*>(geom)); src = g.rec; bytes = (size_t)cfg->P * gsr_rec_stride(cfg->variant) * sizeof(float4); break; }
     case GSR_DBG_POINT_LIST: { BinView b = gsr_carve_bin(cfg->variant, bcap, cfg->W, cfg->H, const_cast<void*>(binning)); src = b.point_list; bytes = (size_t)num_rendered * 4; break; }
     case GSR_DBG_TILE_KEYS: {
         ImgView im = gsr_carve_img(cfg->variant, cfg->W, cfg->H, const_cast<void*>(img));

@@ -248,6 +248,7 @@ static BlendParams make_bp(const gsr_cfg* cfg, GeomView g, BinView b, ImgView im
     p.long_word = nullptr; p.long_len = 0xFFFFFFFFu; p.status = nullptr; p.status_total = nullptr; p.status_cap = 0u;
     p.qmask = b.qmask;                    // the forward's per-(batch, quadrant) cull ballots, read by the splat-parallel backward
     p.ranges = im.ranges; p.point_list = b.point_list; p.cull = g.cull; p.rec = g.rec; p.bg = cfg->bg;
+    p.zero_rec = nullptr;
     p.depth_key = nullptr; p.list_rw = nullptr; p.tile_keys = nullptr; p.scratch_keys = nullptr; p.scratch_ids = nullptr;
     p.sort_buckets = 1; p.list_any_order = 0;
     p.final_T = im.final_T; p.n_contrib = im.n_contrib;

@@ -32,6 +32,8 @@ struct BlendParams {
     const float* dL_dcolor; const float* dL_dothers; const float* dL_dout_all_map; const float* dL_dplane_depth;
     const float* all_map_pixels;
     float* acc;
+    // (last: the forward's kernel arguments keep their offsets)
+    const float4* zero_rec;          // backward: one all-zero record (gsr_blend_sp.hip), what the empty lanes of a 16-entry load fetch; forward: nullptr
 };
 
 // Which tile workgroup b takes (it is observed to run on XCD b % 8, MI355X_MICROARCH.md).  A permutation of the tiles in every case; speed only.

@@ -30,6 +30,7 @@
 // median-normal quirk, no gradient through the 0.99 clamp test); see DESIGN.md "splat-parallel backward".
 #include "gsr_blend_common.h"
 #include <hip/hip_ext.h>
+#include <atomic>
 
 // Waves per SIMD the register budget of each variant is sized for, and the rows of a wave's accumulation table (SP_CAP_*): the measurements behind
 // these values are in DESIGN.md Appendix A (21), (53).
@@ -602,12 +603,15 @@ __global__ void __launch_bounds__(256) SP_OCC k_blend_bwd_sp(BlendParams p)
             const uint32_t e = valid ? (uint32_t)myqueue[pos] : 0u;
             const uint32_t gid = s_ids[e];
             const uint32_t idx0 = cbase + e;                // 0-based position in the tile list == the reference's `contributor`
-            const float4* __restrict__ r = p.rec + (size_t)gid * ST;
+            // an empty lane of the last load fetches the library's all-zero record: ONE pointer select and unconditional loads instead of a select per record
+            // word (which compiled to loads under a per-lane branch plus twenty zero moves).  Such a lane never merges its accumulators (ok == false in every
+            // step), but its u feeds row_scan_add as 0 * u: the words must be finite, and zeros are what they were
+            const float4* __restrict__ r = valid ? p.rec + (size_t)gid * ST : p.zero_rec;
             const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 q0 = valid ? r[0] : z4, q1 = valid ? r[1] : z4, q2 = valid ? r[2] : z4;
+            const float4 q0 = r[0], q1 = r[1], q2 = r[2];
             float4 q3 = z4, q4 = z4;
-            if (V != GSR_EWA) q3 = valid ? r[3] : z4;
-            if (V == GSR_SURFEL) q4 = valid ? r[4] : z4;
+            if (V != GSR_EWA) q3 = r[3];
+            if (V == GSR_SURFEL) q4 = r[4];
             float acc[NREG];
 #pragma unroll
             for (int c = 0; c < NREG; c++) acc[c] = 0.f;
@@ -695,8 +699,28 @@ __global__ void __launch_bounds__(256) SP_OCC k_blend_bwd_sp(BlendParams p)
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 void gsr_blend_bwd_attach_events(hipEvent_t start, hipEvent_t stop) { t_ev_start = start; t_ev_stop = stop; }
 
-int gsr_launch_blend_bwd_sp(const BlendParams& p, int variant, hipStream_t s)
+// The record of no splat: 96 zero bytes (the longest record is the surfel's 80), in the library's own device memory.  Per device, looked up once.
+__device__ float4 g_sp_zero_rec[6];
+static const float4* sp_zero_rec()
 {
+    static std::atomic<const float4*> cache[64];
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
+    const float4* z = cache[d].load(std::memory_order_relaxed);
+    if (!z) {
+        void* a = nullptr;
+        if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_sp_zero_rec)) != hipSuccess) return nullptr;
+        z = reinterpret_cast<const float4*>(a);
+        cache[d].store(z, std::memory_order_relaxed);
+    }
+    return z;
+}
+
+int gsr_launch_blend_bwd_sp(const BlendParams& p0, int variant, hipStream_t s)
+{
+    BlendParams p = p0;
+    p.zero_rec = sp_zero_rec();
+    if (!p.zero_rec) { gsr_set_error("blend backward: the zero record is unavailable"); return 1; }
     dim3 grid(p.gx * p.gy), block(256);
     if (t_ev_start && t_ev_stop) {
         hipEvent_t a = t_ev_start, b = t_ev_stop;

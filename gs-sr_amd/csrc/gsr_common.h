@@ -72,6 +72,8 @@ struct GeomView {
     uint32_t* hist;           // [256 * nblk(P)]
     uint32_t* scan_tmp;       // [>= nblk]
     uint32_t* counters;       // [64] misc device scalars; [0] = num_rendered
+    float* tw_z;              // [P]  SURFEL only (else nullptr): Tw.z = transMat[8], the float of rec[2].x once more, packed -- the one record word the preprocess
+                              //      backward needs (its densification proxy); read out of the 80-byte records it cost a line fetch of the whole record array
     size_t bytes;
 };
 struct BinView {

@@ -350,6 +350,7 @@ __device__ __forceinline__ PreTc pre_surfel_one(const PreParams& p, const int id
     rec[0] = make_float4(T[0], T[1], T[2], T[3]);
     rec[1] = make_float4(T[4], T[5], T[6], T[7]);
     rec[2] = make_float4(T[8], pix, piy, o);
+    p.g.tw_z[idx] = T[8];          // the same float, packed: all the preprocess backward reads of the record (k_preprocess_bwd_surfel)
     rec[3] = make_float4(normal.x, normal.y, normal.z, rgb.x);
     // D = det[Tu Tv Tw] = p . Tw for every pixel's ray-splat vector p = k x l (k, l differ from -Tu, -Tv by multiples of Tw): the blend kernels take the
     // depth s . Tw.xy + Tw.z of SURFEL forward.cu:367 as D / p.z (gsr_blend_sp.hip sp_surf_setup).  Its terms are of size |Tu.z Tv.z Tw| ~ 1e7 against a
@@ -518,7 +519,7 @@ struct PreBwdParams {
     const float *means3D, *shs, *scales, *rots, *cov3D_pre, *view, *proj, *campos;
     const int32_t* radii;
     const uint32_t* clamped;
-    const float4* rec;
+    const float* tw_z;      // SURFEL: GeomView::tw_z
     const float* acc;
     float* acc_clear;       // == acc when the accumulator rows are to be left zeroed (gsr_backward_ex GSR_BWD_LEAVE_ZERO), else nullptr
     gsr_in_grads ig;
@@ -716,7 +717,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_ewa(PreBwdParams p)
         for (int k = 0; k < p.M * 3; k++) dsh[k] = 0.f;
     }
     for (int i = 0; i < 3; i++) ig.dL_dmeans3D[3 * idx + i] = dmean[i];
-    for (int i = 0; i < 6; i++) ig.dL_dcov3D[6 * idx + i] = dcov[i];
+    if (ig.dL_dcov3D) for (int i = 0; i < 6; i++) ig.dL_dcov3D[6 * idx + i] = dcov[i];        // null = not wanted; dcov stays in registers for the scale / rotation chain above
     for (int i = 0; i < 3; i++) ig.dL_dscales[3 * idx + i] = dsc[i];
     for (int i = 0; i < 4; i++) ig.dL_drotations[4 * idx + i] = drot[i];
     if (p.acc_clear) { if (p.variant == GSR_PLANE) clear_acc_row<GSR_ACC_PLANE, GSR_ACC_USED_PLANE>(p.acc_clear, idx); else clear_acc_row<GSR_ACC_EWA, GSR_ACC_USED_EWA>(p.acc_clear, idx); }
@@ -839,7 +840,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_surfel(PreBwdParams p)
             dmean[0] += ds.x; dmean[1] += ds.y; dmean[2] += ds.z;
         }
         // densification proxy (backward.cu:633-636): uses the transMat the blend used and the (possibly updated) dL_dtransMat
-        const float depth = p.rec[(size_t)idx * GSR_REC_SURFEL + 2].x;
+        const float depth = p.tw_z[idx];
         m2x = (float)(dTout[2] * depth * 0.5 * (float)Wb);
         m2y = (float)(dTout[5] * depth * 0.5 * (float)Hb);
     } else if (p.shs && ig.dL_dsh) {
@@ -848,7 +849,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_surfel(PreBwdParams p)
     }
     ig.dL_dmeans2D[3 * idx] = m2x; ig.dL_dmeans2D[3 * idx + 1] = m2y; ig.dL_dmeans2D[3 * idx + 2] = 0.f;
     for (int i = 0; i < 3; i++) ig.dL_dmeans3D[3 * idx + i] = dmean[i];
-    for (int i = 0; i < 9; i++) ig.dL_dcov3D[9 * idx + i] = dTout[i];
+    if (ig.dL_dcov3D) for (int i = 0; i < 9; i++) ig.dL_dcov3D[9 * idx + i] = dTout[i];      // dL_dtransMat: null = the caller has no transMat_precomp to hand it to
     ig.dL_dscales[2 * idx] = dsc[0]; ig.dL_dscales[2 * idx + 1] = dsc[1];
     for (int i = 0; i < 4; i++) ig.dL_drotations[4 * idx + i] = drot[i];
     if (p.acc_clear) clear_acc_row<GSR_ACC_SURFEL, GSR_ACC_USED_SURFEL>(p.acc_clear, idx);
@@ -868,7 +869,7 @@ int gsr_launch_preprocess_bwd(const gsr_cfg* cfg, const gsr_inputs* in, const in
     p.mod = cfg->scale_modifier;
     p.means3D = in->means3D; p.shs = in->shs; p.scales = in->scales; p.rots = in->rotations; p.cov3D_pre = in->cov3D_precomp;
     p.view = cfg->viewmatrix; p.proj = cfg->projmatrix; p.campos = cfg->campos;
-    p.radii = radii; p.clamped = g.clamped; p.rec = g.rec; p.acc = acc; p.acc_clear = leave_zero ? acc : nullptr; p.ig = *ig;
+    p.radii = radii; p.clamped = g.clamped; p.tw_z = g.tw_z; p.acc = acc; p.acc_clear = leave_zero ? acc : nullptr; p.ig = *ig;
     dim3 grid(gsr_div_up(cfg->P, 256)), block(256);
     const bool sh16 = p.shs && p.ig.dL_dsh && cfg->M == 16 && ((((uintptr_t)p.shs) | ((uintptr_t)p.ig.dL_dsh)) & 15) == 0;
     if (cfg->variant == GSR_SURFEL) { if (sh16) hipLaunchKernelGGL(k_preprocess_bwd_surfel<true>, grid, block, 0, s, p); else hipLaunchKernelGGL(k_preprocess_bwd_surfel<false>, grid, block, 0, s, p); }

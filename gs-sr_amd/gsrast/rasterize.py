@@ -239,8 +239,9 @@ def forward(variant, means3D, sh, colors_precomp, opacities, scales, rotations, 
 
 def backward(variant, num_rendered, settings, radii, means3D, sh, colors_precomp, opacities, scales, rotations,
              cov3Ds_precomp, all_map, geom, binning, img, grad_color, grad_others=None, grad_all_map=None,
-             grad_plane_depth=None, all_map_pixels=None):
-    """Returns dict of gradients (tensors shaped like the reference's RasterizeGaussiansBackwardCUDA outputs)."""
+             grad_plane_depth=None, all_map_pixels=None, want_dcov3D=True):
+    """Returns dict of gradients (tensors shaped like the reference's RasterizeGaussiansBackwardCUDA outputs).  want_dcov3D=False: dL_dcov3D
+    (the surfel's dL_dtransMat) is neither allocated nor stored -- the library gets a null pointer for it -- and comes back as None."""
     L = lib()
     dev = means3D.device
     cfg, inp, keep, P, M = _prepare(variant, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -249,7 +250,7 @@ def backward(variant, num_rendered, settings, radii, means3D, sh, colors_precomp
     mk = torch.zeros if P == 0 else torch.empty
     g = dict(dL_dmeans3D=mk((P, 3), **f32), dL_dmeans2D=mk((P, 3), **f32),
              dL_dcolors=mk((P, 3), **f32), dL_dopacity=mk((P, 1), **f32),
-             dL_dcov3D=mk((P, 9 if variant == SURFEL else 6), **f32),
+             dL_dcov3D=mk((P, 9 if variant == SURFEL else 6), **f32) if want_dcov3D else None,
              dL_dsh=mk((P, M, 3), **f32), dL_dscales=mk((P, 2 if variant == SURFEL else 3), **f32),
              dL_drotations=mk((P, 4), **f32))
     if variant == PLANE:
@@ -329,13 +330,15 @@ class _RasterizeGaussians(torch.autograd.Function):
          all_map, all_map_pixels) = ctx.saved_tensors
         pos = (variant, ctx.num_rendered, rs, radii, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map,
                geomBuffer, binningBuffer, imgBuffer)
+        # cov3Ds_precomp not supplied (the empty tensor of exactly_one_of): its gradient slot has no taker -- 10.8 MB per surfel backward at P = 300k
+        want_dcov3D = cov3Ds_precomp is not None and cov3Ds_precomp.numel() != 0
         kw = dict(grad_color=grad_color)
         if variant == SURFEL:
             kw.update(grad_others=more[0])
         elif variant == PLANE:               # more = the gradients of (out_observe, out_all_map, plane_depth)
             kw.update(grad_all_map=more[1], grad_plane_depth=more[2])
         g = _snapshot(rs.debug, pos[3:] + tuple(kw.values()), "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
-                      lambda: backward(*pos, all_map_pixels=all_map_pixels, **kw))
+                      lambda: backward(*pos, all_map_pixels=all_map_pixels, want_dcov3D=want_dcov3D, **kw))
         # (variant, means3D, means2D, means2D_abs, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, all_map, raster_settings)
         return (None, g["dL_dmeans3D"], g["dL_dmeans2D"], g.get("dL_dmeans2D_abs"), g["dL_dsh"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dscales"],
                 g["dL_drotations"], g["dL_dcov3D"], g.get("dL_dall_map"), None)

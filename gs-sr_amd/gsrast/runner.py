@@ -102,7 +102,8 @@ def run_raw(variant, sc, device="cuda"):
               tile_keys=rd(5, (max(R, 1),), torch.int32).view(np.uint32)[:R],
               ranges=rd(2, (gx * gy, 2), torch.int32).view(np.uint32),
               final_T=rd(3, (k, H, W), torch.float32),
-              n_contrib=rd(4, (k2, H, W), torch.int32).view(np.uint32))
+              n_contrib=rd(4, (k2, H, W), torch.int32).view(np.uint32),
+              rec=rd(6, (max(P, 1), 4 * {"ewa": 3, "plane": 4, "surfel": 5}[variant]), torch.float32)[:P])      # packed blend records
     st.update({kk: v.cpu().numpy() for kk, v in outs.items()})
     torch.cuda.synchronize()
     return st

@@ -103,7 +103,7 @@ typedef struct gsr_in_grads {        /* all written in full by the library (no z
     float* dL_dmeans2D_abs; /* PLANE [P,3] or NULL */
     float* dL_dcolors;      /* [P,3] */
     float* dL_dopacity;     /* [P]   */
-    float* dL_dcov3D;       /* [P,6] (SURFEL: dL_dtransMat [P,9]) */
+    float* dL_dcov3D;       /* [P,6] (SURFEL: dL_dtransMat [P,9]), or NULL = not wanted (no cov3D_precomp to hand it to): the store is skipped */
     float* dL_dsh;          /* [P,M,3] or NULL when M == 0 */
     float* dL_dscales;      /* [P,3] (SURFEL [P,2]) */
     float* dL_drotations;   /* [P,4] */
@@ -929,7 +929,8 @@ enum gsr_debug_field {
     GSR_DBG_RANGES = 2,        /* uint32 [T,2]                                    (from img)     */
     GSR_DBG_FINAL_T = 3,       /* float  [N] (SURFEL [3,N])                       (from img)     */
     GSR_DBG_N_CONTRIB = 4,     /* uint32 [N] (SURFEL [2,N])                       (from img)     */
-    GSR_DBG_TILE_KEYS = 5      /* uint32 [R] tile id per sorted instance          (from binning) */
+    GSR_DBG_TILE_KEYS = 5,     /* uint32 [R] tile id per sorted instance          (from binning) */
+    GSR_DBG_REC = 6            /* float  [P,4S] packed blend records, S = 3 EWA / 4 PLANE / 5 SURFEL float4 (from geom) */
 };
 int gsr_debug_read(const gsr_cfg* cfg, int32_t field, const void* geom, const void* binning, size_t binning_bytes,
                    const void* img, uint32_t num_rendered, void* dst, void* stream);
