@@ -539,7 +539,7 @@ def _hip_outputs(hr, variant, sc, og):
     return st, cand
 
 
-def _check_against_truth(hr, variant, cm, sc, og):
+def _check_against_truth(hr, variant, cm, sc, og, row_groups=None):
     """Integer stages bit-exact against the float32 oracle; everything else against the FLOAT64 truth (tests/parity_truth.py): exact indices and
     the nominal 1e-4 on every pixel whose gate decisions are robust under float32 rounding, every other mismatch attributed to a named gate,
     gradients within max(1e-3, 2 x the float32 oracle's own error vs the truth)."""
@@ -548,7 +548,7 @@ def _check_against_truth(hr, variant, cm, sc, og):
     f32, fma, truth, ints = pt.run_oracles(sc, variant, og, hip_state=st, fma=sc["means3D"].shape[0] <= 50000)     # incl. the filtered instance list against the oracle's (tests/tile_cull.py)
     assert np.array_equal(st["radii"], ints["radii"])
     cand["n_contrib"] = ints["view"]["n_contrib"]                             # positions in the oracle's list
-    rep = pt.check_case(variant, cm, cand, f32, fma, truth)
+    rep = pt.check_case(variant, cm, cand, f32, fma, truth, row_groups=row_groups)
     rep["tile_instances"] = {k: v for k, v in ints["view"].items() if k not in ("keep", "n_contrib")}
     rep["hip_grads"] = cand["grads"]; rep["hip_color"] = cand["color"]
     return rep
