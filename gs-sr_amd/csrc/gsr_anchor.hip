@@ -47,7 +47,8 @@ __device__ __forceinline__ bool anc_entry(uint32_t i, const gsr_anchor_level& L,
     }
     const uint32_t j = i - Na, a = j / (uint32_t)L.k;
     const float g = L.grads[j];
-    if (!(g >= L.thr_lo && g < L.thr_hi) || !L.offset_mask[j]) return false;
+    // an infinite thr_hi is no upper bound (Scaffold-GS, Octree pass B: `grads >= threshold` alone): a gradient of +inf is a candidate; NaN never is
+    if (!(g >= L.thr_lo && (g < L.thr_hi || L.thr_hi == INFINITY)) || !L.offset_mask[j]) return false;
     if (L.rand && !(L.rand[j] > L.rand_thr)) return false;
     if (L.mask && !L.mask[a]) return false;
     const float* sc = L.scaling + (size_t)a * L.scaling_stride;

@@ -8,11 +8,16 @@ import torch
 from . import call, dev_f32
 
 
+def _aligned16(t):
+    """The kernels read a quaternion as one 16-byte word: a contiguous view that starts 4 or 8 bytes into its storage is copied."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 class _GaussActivations(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling_raw, rotation_raw, opacity_raw):
         s = dev_f32(scaling_raw, "scaling", allow_empty=False)
-        q = dev_f32(rotation_raw, "rotation", allow_empty=False)
+        q = _aligned16(dev_f32(rotation_raw, "rotation", allow_empty=False))
         o = dev_f32(opacity_raw, "opacity", allow_empty=False)
         P = s.shape[0]
         if s.dim() != 2 or not (1 <= s.shape[1] <= 3) or q.shape != (P, 4) or o.numel() != P:
@@ -28,7 +33,7 @@ class _GaussActivations(torch.autograd.Function):
         so, q, qo, oo = ctx.saved_tensors
         P = so.shape[0]
         c = lambda g: None if g is None else g.contiguous()
-        gs, gq, go = c(gs), c(gq), c(go)
+        gs, gq, go = c(gs), _aligned16(c(gq)), c(go)
         ds, dq, do = torch.empty_like(so), torch.empty_like(q), torch.empty_like(oo)
         call("gsr_gauss_activations_backward", so.device, P, int(so.shape[1]), so, q, qo, oo, gs, gq, go, ds, dq, do)
         return ds, dq, do

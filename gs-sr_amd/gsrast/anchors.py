@@ -39,8 +39,8 @@ def _grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cel
     """-> (new_anchor [U,3], new_feat [U,F], the number of new cells before the weed-out).
 
     anchor [Na,3]: the first n0 (default: all) own the candidate slots offset [n0,k,3] / grads [n0*k] / offset_mask [n0*k]; the others only occupy
-    cells.  scaling [n0,>=3] is the ACTIVATED scaling, anchor_feat [n0,F].  Slot j is a candidate iff thr_lo <= grads[j] < thr_hi, offset_mask[j],
-    rand[j] > rand_thr (rand given) and mask[j // k] (mask [n0] given; a masked-out original anchor does not occupy its cell either).  The new
+    cells.  scaling [n0,>=3] is the ACTIVATED scaling, anchor_feat [n0,F].  Slot j is a candidate iff thr_lo <= grads[j] < thr_hi (thr_hi = inf: no
+    upper bound, a gradient of +inf is a candidate), offset_mask[j], rand[j] > rand_thr (rand given) and mask[j // k] (mask [n0] given; a masked-out original anchor does not occupy its cell either).  The new
     anchors are the distinct cells rint((anchor + offset * scaling - origin) / cell) of the candidates that hold no admitted anchor, in (x, y, z)
     order, at cell * c + origin, with the element-wise maximum of the candidates' features.  One host synchronisation (the count).
     Octree-GS: occupy [n0] given, original anchor a occupies its cell iff occupy[a] and mask decides candidacy alone; weed (a gsr_octree_weed of

@@ -458,7 +458,8 @@ int gsr_loss_plane_mv_scale(size_t n_depth, size_t n_near, size_t n_am, const fl
  * OctreeGaussian.anchor_growing (octree_gaussian.py:401-534).  anchor [Na,3]: the first N0 are the original anchors and own the N0*k candidate
  * slots; the rest were added at earlier levels and only occupy cells.  mask [N0] bytes or NULL: the slots of anchor a may be candidates, and its
  * cell counts as occupied, only where mask[a] != 0 (anchors >= N0 always occupy).  Slot j of anchor a = j / k is a candidate iff
- *   thr_lo <= grads[j] < thr_hi  and  offset_mask[j]  and  (rand == NULL or rand[j] > rand_thr)  and  the mask admits a;
+ *   thr_lo <= grads[j] < thr_hi  and  offset_mask[j]  and  (rand == NULL or rand[j] > rand_thr)  and  the mask admits a
+ * (thr_hi = +inf is no upper bound: grads[j] = +inf is then a candidate; a NaN gradient never is);
  * its point is p = anchor[a] + offset[j] * scaling[a,:3] (a multiply, then an add) and its cell c = rint((p - origin) / cell) (round-half-even,
  * IEEE division), all in float32 with every operation rounded on its own.  Result: the distinct candidate cells that hold no admitted anchor,
  * in lexicographic signed (x, y, z) order (torch.unique(dim=0)); new_anchor = float(c) * cell + origin; new_feat [.,F] = the element-wise maximum

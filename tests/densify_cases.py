@@ -1,5 +1,6 @@
 """Inputs for the densify_and_prune tests and tools: random scenes whose every compared quantity keeps a relative distance of 1e-5 from its
-threshold (so that no selection hangs on the last bit of an exp, a sigmoid or a quotient), and a model object with the reference's attributes."""
+threshold (so that no selection hangs on the last bit of an exp, a sigmoid or a quotient), and a model object with the reference's attributes.
+The thresholds themselves are met by tests/densify_edge_cases.py, which hands the activated tensors over."""
 import types
 
 import numpy as np

@@ -34,7 +34,9 @@ def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, *, cell
     N0 = Na if n0 is None else n0
     k = offset.shape[1]
     grads = grads.reshape(-1)
-    cand = (grads >= _f32(thr_lo, grads)) & (grads < _f32(thr_hi, grads)) & offset_mask.reshape(-1).bool()
+    cand = (grads >= _f32(thr_lo, grads)) & offset_mask.reshape(-1).bool()
+    if thr_hi != math.inf:                                           # thr_hi = +inf is no upper bound: a gradient of +inf is a candidate
+        cand &= grads < _f32(thr_hi, grads)
     if rand is not None:
         cand &= rand.reshape(-1) > _f32(rand_thr, grads)
     occupied = torch.ones(Na, dtype=torch.bool, device=anchor.device)

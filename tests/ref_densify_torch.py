@@ -47,8 +47,13 @@ def _grads(accum, denom):
 
 
 def classify(accum, denom, s_act, o_act, radii, *, max_grad, min_opacity, extent, percent_dense, max_screen_size, N=2, accum_abs=None, denom_abs=None,
-             abs_max_grad=None, abs_split_radii2D_threshold=20.0, max_abs_split_points=None, max_all_points=None):
-    """-> clone, split, prune_self, prune_child masks over the originals (bool [P])."""
+             abs_max_grad=None, abs_split_radii2D_threshold=20.0, max_abs_split_points=None, max_all_points=None, child_rule="reference"):
+    """-> clone, split, prune_self, prune_child masks over the originals (bool [P]).
+    child_rule: how a child's world-size test is taken.  "reference": max(exp(log(s / (0.8 N)))) > 0.1 extent, the reference's own chain of torch
+    operations; "quotient": max(s) / float32(0.8 N) > 0.1 extent, one IEEE division -- the contract of include/gsrast.h.  The two
+    agree except within a few float32 steps of the threshold (measured: tests/test_densify_edges_cpu.py)."""
+    if child_rule not in ("reference", "quotient"):
+        raise ValueError(f"child_rule: expected 'reference' or 'quotient' but found {child_rule!r}")
     P = s_act.shape[0]
     g = _grads(accum, denom)
     ms = s_act.max(dim=1).values if P else s_act.new_zeros(0)
@@ -80,9 +85,13 @@ def classify(accum, denom, s_act, o_act, radii, *, max_grad, min_opacity, extent
     prune_self, prune_child = low, low
     if max_screen_size:
         # the screen-size term compares statistics that were re-allocated as zeros: it never holds
-        child_act = torch.exp(torch.log(s_act / (0.8 * N)))
         prune_self = low | (ms > 0.1 * extent)
-        prune_child = low | ((child_act.max(dim=1).values if P else ms) > 0.1 * extent)
+        if child_rule == "reference":
+            child_act = torch.exp(torch.log(s_act / (0.8 * N)))
+            child_ms = child_act.max(dim=1).values if P else ms
+        else:
+            child_ms = ms / torch.tensor(0.8 * N, dtype=torch.float32, device=ms.device)
+        prune_child = low | (child_ms > 0.1 * extent)
     return clone, split, prune_self, prune_child
 
 

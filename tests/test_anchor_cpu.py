@@ -2,6 +2,7 @@
 ScaffoldGaussian.adjust_anchor produced (tests/golden/make_golden_anchor.py), bit for bit; the header declarations; and the argument errors of
 gsrast.anchors, which are raised before any device call."""
 import glob
+import math
 import os
 import re
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import anchor_edge_cases as E
 import ref_anchor_torch as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -168,3 +170,96 @@ def test_python_argument_errors_name_the_argument():
     m.n_offsets, m.voxel_size, m.update_depth, m.update_init_factor, m.update_hierachy_factor = k, 0.01, 3, 16, 4
     with pytest.raises(RuntimeError, match="model._anchor must be a CUDA tensor"):
         anchors.adjust_anchor_(m)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the selection thresholds
+# tests/anchor_edge_cases.py: slots named by the comparison they sit on.  Here, without a device: the restatement admits exactly the names the
+# literal rule admits, and reversing any one comparison of the rule changes the names -- so the device tests, which demand these names, fail on a
+# kernel with that comparison reversed.
+BAND = [(0.0002, 0.0009, 0.3)]                                        # the Octree pass A shape: a finite upper threshold
+OPEN = [(0.0002, math.inf, 0.3)]                                      # Scaffold-GS and the Octree pass B: no upper threshold
+GROWING = [(0.0002 * 2 ** i, math.inf, 0.5 ** (i + 1)) for i in range(3)]   # anchors.anchor_growing: threshold * (4 // 2) ** i, 0.5 ** (i + 1)
+
+
+def _grow(sc, level, **kw):
+    lo, hi, rt = sc["levels"][level]
+    return R.grow_level(sc["anchor"], sc["offset"], sc["scaling"], sc["feat"], sc["grads"], sc["seen"], cell=E.CELL, thr_lo=lo, thr_hi=hi,
+                        rand=sc["rand"][level], rand_thr=rt, **kw)
+
+
+@pytest.mark.parametrize("levels", [BAND, OPEN], ids=["band", "open"])
+def test_threshold_slots_restatement_equals_the_literal_rule(levels):
+    sc = E.scene(levels, seed=11)
+    a, f = _grow(sc, 0)
+    want = E.expected_names(sc, 0)
+    assert E.names_of(sc, 0, a) == want
+    q = lambda *n: (0,) + n in want
+    assert not q("lo", "below") and q("lo", "on") and q("lo", "above")                       # >=
+    assert not q("rand", "below") and not q("rand", "on") and q("rand", "above")             # strict >
+    assert not q("nan", "grad") and not q("-inf", "grad") and q("control", "in") and not q("control", "out")
+    if levels is BAND:
+        assert q("hi", "below") and not q("hi", "on") and not q("hi", "above") and not q("+inf", "grad")      # strict <
+    else:
+        assert q("+inf", "grad")                                                             # scaffold_gaussian.py:561: grads >= threshold, nothing else
+    # every named value sits where its name says, bit for bit
+    g, r = sc["grads"].numpy(), sc["rand"][0].numpy()
+    lo, hi, rt = (np.float32(v) for v in levels[0])
+    for (l, what, side), (_, j) in sc["names"].items():
+        v, t = {"lo": (g[j], lo), "hi": (g[j], hi), "rand": (r[j], rt)}.get(what, (None, None))
+        if v is not None:
+            assert {"below": np.nextafter(t, np.float32(-np.inf)), "on": t, "above": np.nextafter(t, np.float32(np.inf))}[side] == v, (what, side)
+
+
+def test_infinite_gradient_against_a_literal_mask():
+    """+inf with no upper threshold is a candidate (the reference: candidate_mask = grads >= cur_threshold)."""
+    sc = E.scene(OPEN, seed=12)
+    a, _ = _grow(sc, 0)
+    literal = (sc["grads"] >= torch.tensor(0.0002, dtype=torch.float32)) & (sc["rand"][0] > torch.tensor(0.3, dtype=torch.float32))
+    named = {j: name for name, (_, j) in sc["names"].items()}
+    want = sorted(named[j] for j in torch.nonzero(literal).reshape(-1).tolist() if j in named)
+    assert (0, "+inf", "grad") in want and E.names_of(sc, 0, a) == want
+
+
+@pytest.mark.parametrize("flip", E.FLIPS)
+def test_every_admission_comparison_is_observable(flip):
+    changed = []
+    for tag, levels in (("band", BAND), ("open", OPEN), ("growing", GROWING)):
+        sc = E.scene(levels, seed=13)
+        for l in range(len(levels)):
+            base, other = E.expected_names(sc, l), E.expected_names(sc, l, flip)
+            if base != other:
+                changed.append((tag, l, sorted(set(base) ^ set(other))))
+    print(flip, changed)
+    assert changed, flip
+    if flip in ("lo", "rand"):
+        assert {c[:2] for c in changed} >= {("growing", 0), ("growing", 1), ("growing", 2)}   # at every level's own threshold
+
+
+def test_anchor_growing_thresholds_per_level():
+    sc = E.scene(GROWING, seed=14)
+    d, counts = R.anchor_growing(sc["anchor"], sc["offset"], sc["scaling"], sc["feat"], sc["grads"], sc["seen"], 0.0002, voxel_size=E.CELL / 16,
+                                 n_offsets=E.K, rand=sc["rand"])
+    p = 0
+    for l, c in enumerate(counts):
+        assert c > 0 and E.names_of(sc, l, d["anchor"][p:p + c]) == E.expected_names(sc, l), l
+        p += c
+
+
+@pytest.mark.parametrize("case", list(E.WEED_CASES))
+@pytest.mark.parametrize("mode", ["floor", "round", "ceil"])
+def test_weed_out_threshold_cases(case, mode):
+    import ref_anchor_octree_torch as RO
+    C, t_count, thr = E.WEED_CASES[case]
+    pos, lv, cams, visible, il = E.weed_case(C, t_count, seed=C, mode=mode)
+    pred = RO.pred_levels(pos, cams, E.WEED["sd"], E.WEED["fork"], torch.float64)
+    shift = 0.5 if mode == "round" else 0.0
+    assert float((pred - shift - torch.round(pred - shift)).abs().min()) >= 0.2              # the margin of the existing weed-out tests
+    count, keep = RO.weed_out(pos, lv, cams, E.WEED["sd"], E.WEED["fork"], E.WEED["levels"], mode, thr)
+    assert torch.equal(count, visible)
+    want = E.weed_keep(visible.numpy(), C, thr)
+    assert np.array_equal(keep.numpy(), want)
+    assert np.array_equal(want, visible.numpy() > t_count)                                   # strict: t * C itself is dropped
+    assert np.float32(t_count) / np.float32(C) == np.float32(thr)                            # the middle count sits ON the threshold
+    assert not np.array_equal(E.weed_keep(visible.numpy(), C, thr, flip=True), want)         # `>=` would keep it
+    if C > 256:
+        assert (il[256:] >= 1).any() and (il[:256] >= 1).any()                               # the count is carried across the chunks

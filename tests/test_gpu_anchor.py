@@ -1,6 +1,7 @@
 """Anchor growing + pruning on the device (gsrast.anchors; gs-sr_amd/csrc/gsr_anchor.hip).  Every comparison is exact equality:
 against the fixtures the reference's own ScaffoldGaussian.adjust_anchor produced (tests/golden/make_golden_anchor.py) and, on randomised scenes,
-against the torch restatement that test_anchor_cpu.py holds to those fixtures (tests/ref_anchor_torch.py)."""
+against the torch restatement that test_anchor_cpu.py holds to those fixtures (tests/ref_anchor_torch.py).  The randomised scenes do not meet a
+threshold; the last section puts slots one float32 below, on and above each of them (tests/anchor_edge_cases.py)."""
 import glob
 import math
 import os
@@ -314,3 +315,55 @@ def test_short_training_loop_with_densification():
     assert len(set(counts)) > 1, counts                               # the anchor count changed at least once
     assert all(math.isfinite(x) for x in losses)
     assert sum(losses[-5:]) / 5 <= losses[0], (losses[0], losses[-5:])
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the selection thresholds
+# tests/anchor_edge_cases.py: every slot named by the comparison it sits on (one float32 below, on, one above), in a cell of its own.  The names
+# that show are demanded literally and through the restatement; test_anchor_cpu.py shows that reversing any comparison changes them.
+import anchor_edge_cases as E                                      # noqa: E402
+
+BAND = [(0.0002, 0.0009, 0.3)]
+OPEN = [(0.0002, math.inf, 0.3)]
+GROWING = [(0.0002 * 2 ** i, math.inf, 0.5 ** (i + 1)) for i in range(3)]
+
+
+def _dev(sc):
+    return [sc[n].to(DEV) for n in ("anchor", "offset", "scaling", "feat", "grads", "seen")]
+
+
+@pytest.mark.parametrize("levels", [BAND, OPEN], ids=["band", "open"])
+def test_grow_level_on_both_sides_of_every_threshold(levels):
+    """thr_lo is `>=`, a finite thr_hi a strict `<`, rand a strict `>`; NaN and -inf are never candidates; +inf is one iff thr_hi is +inf (Scaffold-GS
+    and the Octree pass B have no upper threshold: the kernel rejected it while it compared g < +inf)."""
+    from gsrast import anchors
+    lo, hi, rt = levels[0]
+    sc = E.scene(levels, seed=21)
+    host = [sc[n] for n in ("anchor", "offset", "scaling", "feat", "grads", "seen")]
+    want_a, want_f = R.grow_level(*host, cell=E.CELL, thr_lo=lo, thr_hi=hi, rand=sc["rand"][0], rand_thr=rt)
+    got_a, got_f = anchors.grow_level(*_dev(sc), cell=E.CELL, thr_lo=lo, thr_hi=hi, rand=sc["rand"][0].to(DEV), rand_thr=rt)
+    names = E.names_of(sc, 0, got_a)
+    assert names == E.expected_names(sc, 0), sorted(set(names) ^ set(E.expected_names(sc, 0)))
+    assert ((0, "+inf", "grad") in names) == (levels is OPEN) and (0, "lo", "on") in names and (0, "rand", "on") not in names
+    assert got_a.shape == want_a.shape and torch.equal(got_a.cpu(), want_a) and torch.equal(got_f.cpu(), want_f)
+    if levels is OPEN:                                              # the default thr_hi is the same open end
+        again, _ = anchors.grow_level(*_dev(sc), cell=E.CELL, thr_lo=lo, rand=sc["rand"][0].to(DEV), rand_thr=rt)
+        assert torch.equal(again, got_a)
+
+
+def test_anchor_growing_on_both_sides_of_every_level_threshold():
+    """Three levels with the thresholds as anchors.anchor_growing computes them: threshold * 2 ** i against the gradient, 0.5 ** (i + 1) against the draw."""
+    from gsrast import anchors
+    sc = E.scene(GROWING, seed=22)
+    host = [sc[n] for n in ("anchor", "offset", "scaling", "feat", "grads", "seen")]
+    kw = dict(voxel_size=E.CELL / 16, n_offsets=E.K)
+    want, counts = R.anchor_growing(*host, 0.0002, rand=sc["rand"], **kw)
+    got = anchors.anchor_growing(*_dev(sc), 0.0002, rand=[x.to(DEV) for x in sc["rand"]], **kw)
+    assert all(c > 0 for c in counts) and got["anchor"].shape[0] == sum(counts)
+    p = 0
+    for l, c in enumerate(counts):
+        names = E.names_of(sc, l, got["anchor"][p:p + c])
+        assert names == E.expected_names(sc, l), (l, sorted(set(names) ^ set(E.expected_names(sc, l))))
+        assert (l, "+inf", "grad") in names and (l, "nan", "grad") not in names
+        p += c
+    for n in NAMES:
+        assert got[n].shape == want[n].shape and torch.equal(got[n].cpu(), want[n]), n

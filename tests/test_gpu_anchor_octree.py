@@ -1,7 +1,8 @@
 """Octree-GS anchor growing + pruning on the device (gsrast.anchors.octree_adjust_anchor_, gsrast.octree.weed_out; gs-sr_amd/csrc/gsr_anchor.hip).
 Whole calls are compared by exact equality: against the fixtures the reference's own OctreeGaussian.adjust_anchor produced
 (tests/golden/make_golden_anchor_octree.py, whose margins keep that honest) and, on randomised scenes without a knife edge, against the torch
-restatement that test_anchor_octree_cpu.py holds to those fixtures.  The weed-out alone is compared with a float64 evaluation."""
+restatement that test_anchor_octree_cpu.py holds to those fixtures.  The weed-out alone is compared with a float64 evaluation.  The knife edges
+those scenes avoid have tests of their own at the end: the visible threshold and the gradient band on both sides (tests/anchor_edge_cases.py)."""
 import functools
 import glob
 import math
@@ -312,3 +313,41 @@ def test_errors():
         anchors.octree_adjust_anchor_(m, 3000)
     with pytest.raises(RuntimeError, match="positions must be a CUDA tensor"):
         octree.weed_out(pos.cpu(), lv, cams, 16.0, 2, 6, "round", 0.3)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the selection thresholds
+import anchor_edge_cases as E                                      # noqa: E402
+
+
+@pytest.mark.parametrize("case", list(E.WEED_CASES))
+@pytest.mark.parametrize("mode", MODES)
+def test_weed_out_on_both_sides_of_the_visible_threshold(case, mode):
+    """Positions that exactly t*C - 1, t*C and t*C + 1 cameras admit (pred 0.25 from every boundary): visible / C > t is strict, so t*C itself is
+    dropped -- 2/8 against 0.25, 3/10 against float32(0.3) (the quotient rounds to the same float), 65/260 with the count carried over two LDS chunks."""
+    from gsrast import octree
+    C, t_count, thr = E.WEED_CASES[case]
+    pos, lv, cams, visible, _ = E.weed_case(C, t_count, seed=C, mode=mode)
+    want_count, want_keep = R.weed_out(pos, lv, cams, E.WEED["sd"], E.WEED["fork"], E.WEED["levels"], mode, thr)
+    count, keep = octree.weed_out(pos.to(DEV), lv.to(DEV), cams.to(DEV), E.WEED["sd"], E.WEED["fork"], E.WEED["levels"], mode, thr)
+    assert torch.equal(count.cpu(), visible) and torch.equal(want_count, visible), count.tolist()
+    assert torch.equal(keep.cpu(), visible > t_count) and torch.equal(keep.cpu(), want_keep), keep.tolist()
+
+
+def test_octree_passes_and_an_infinite_gradient():
+    """The level with the Octree loop's arguments (per-anchor mask, occupancy apart): pass A's band [thr, ds_thr) rejects a gradient of +inf, pass B
+    (no upper threshold) admits it."""
+    from gsrast import anchors
+    sc = E.scene([(0.0002, 0.0009, 0.3)], seed=31)
+    host = [sc[n] for n in ("anchor", "offset", "scaling", "feat", "grads", "seen")]
+    dev = [t.to(DEV) for t in host]
+    mask = torch.ones(E.N_ANCHORS, dtype=torch.bool)
+    for thr_hi, level_names in ((0.0009, [(0.0002, 0.0009, 0.3)]), (math.inf, [(0.0002, math.inf, 0.3)])):
+        sc["levels"] = level_names
+        want_a, want_f = R.grow_pass(sc["anchor"], mask, sc["offset"], sc["scaling"], sc["feat"], sc["grads"],
+                                     (sc["grads"] >= torch.tensor(0.0002)) & ((sc["grads"] < torch.tensor(thr_hi)) if thr_hi != math.inf else mask.repeat_interleave(E.K))
+                                     & (sc["rand"][0] > torch.tensor(0.3)), cell=E.CELL, origin=(0.0, 0.0, 0.0))
+        got_a, got_f = anchors.grow_level(*dev, cell=E.CELL, thr_lo=0.0002, thr_hi=thr_hi, rand=sc["rand"][0].to(DEV), rand_thr=0.3, mask=mask.to(DEV),
+                                          occupy=mask.to(DEV))
+        names = E.names_of(sc, 0, got_a)
+        assert names == E.expected_names(sc, 0) and ((0, "+inf", "grad") in names) == (thr_hi == math.inf)
+        assert torch.equal(got_a.cpu(), want_a) and torch.equal(got_f.cpu(), want_f)

@@ -79,18 +79,18 @@ def test_fixture(case, opt):
     _step(m, rows)
 
 
-def _random_model(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), **kw):
+def _random_model(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), N=2, **kw):
     spec = KINDS[kind]
-    p, mom, stats = DC.make_inputs(P, seed, cols=spec["cols"], rest=rest, pgsr=spec["pgsr"], device=DEV, frac=frac)
+    p, mom, stats = DC.make_inputs(P, seed, cols=spec["cols"], rest=rest, pgsr=spec["pgsr"], device=DEV, frac=frac, N=N)
     m = DC.Model(p, mom, stats, DEV, optimizer=opt, pgsr=spec["pgsr"], with_state=with_state, **kw)
     return m, p, mom, stats
 
 
-def _noise(m, stats, pgsr, rules, seed):
+def _noise(m, stats, pgsr, rules, seed, N=2):
     kw = dict(accum_abs=m.xyz_gradient_accum_abs, denom_abs=m.denom_abs, max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points) if pgsr else {}
-    clone, split, _, _ = R.classify(m.xyz_gradient_accum, m.denom, m.get_scaling.detach(), m.get_opacity.detach(), m.max_radii2D, **rules, **kw)
+    clone, split, _, _ = R.classify(m.xyz_gradient_accum, m.denom, m.get_scaling.detach(), m.get_opacity.detach(), m.max_radii2D, N=N, **rules, **kw)
     g = torch.Generator(device=DEV); g.manual_seed(seed)
-    return torch.randn(2 * int(split.sum()), 3, device=DEV, generator=g), torch.randn(int(clone.sum()), 3, device=DEV, generator=g)
+    return torch.randn(N * int(split.sum()), 3, device=DEV, generator=g), torch.randn(int(clone.sum()), 3, device=DEV, generator=g)
 
 
 def _rules(pgsr, max_screen_size=20, **kw):
@@ -101,20 +101,20 @@ def _rules(pgsr, max_screen_size=20, **kw):
     return r
 
 
-def _run_random(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), rules_kw=None, **model_kw):
+def _run_random(kind, P, seed, opt="gsrast", with_state=True, rest=15, frac=(0.10, 0.10, 0.05), rules_kw=None, N=2, **model_kw):
     pgsr = KINDS[kind]["pgsr"]
     rules = _rules(pgsr, **(rules_kw or {}))
-    m, p, mom, stats = _random_model(kind, P, seed, opt, with_state, rest, frac, **model_kw)
+    m, p, mom, stats = _random_model(kind, P, seed, opt, with_state, rest, frac, N=N, **model_kw)
     s_act, o_act = m.get_scaling.detach().clone(), m.get_opacity.detach().clone()
-    z_split, z_clone = _noise(m, stats, pgsr, rules, seed)
+    z_split, z_clone = _noise(m, stats, pgsr, rules, seed, N=N)
     lay_rules = dict(rules)
     if pgsr:
         lay_rules.update(max_all_points=m.max_all_points, max_abs_split_points=m.max_abs_split_points)
-    L = DC.run_layout(p, mom if with_state else {}, stats, s_act, o_act, z_split, z_clone, pgsr, lay_rules, device=DEV)
-    n = _call(m, rules, pgsr, noise_split=z_split, noise_clone=z_clone if pgsr else None)
+    L = DC.run_layout(p, mom if with_state else {}, stats, s_act, o_act, z_split, z_clone, pgsr, lay_rules, device=DEV, N=N)
+    n = _call(m, rules, pgsr, noise_split=z_split, noise_clone=z_clone if pgsr else None, N=N)
     assert n == L["counts"]["rows"]
     _check_model_state(m, n, pgsr, had_state=with_state)
-    worst = DC.check_against_layout(m.tensors(), m.moments(), L, p, s_act, z_split, z_clone, pgsr, what=f"{kind} P={P}")
+    worst = DC.check_against_layout(m.tensors(), m.moments(), L, p, s_act, z_split, z_clone, pgsr, N=N, what=f"{kind} P={P} N={N}")
     return m, L, worst
 
 
@@ -188,12 +188,9 @@ def test_edge_cases(kind):
     # degree 0: an f_rest of zero width keeps its shape
     m, L, _ = _run_random(kind, 2000, seed=4, rest=0)
     assert m._features_rest.shape == (L["counts"]["rows"], 0, 3)
-    # more children than two
-    from gsrast import densify
-    m, p, mom, stats = _random_model(kind, 1500, 8, rest=3)
-    rules = _rules(pgsr)
-    n = densify.densify_and_prune_(m, rules["max_grad"], rules["min_opacity"], rules["extent"], None, abs_max_grad=rules["abs_max_grad"] if pgsr else None, N=3)
-    assert n == m._xyz.shape[0] and torch.isfinite(m._xyz).all()
+    # more children than two: counts, map, every copied row and the computed columns against the restatement (N = 1 and 4: test_gpu_densify_edges.py)
+    m, L, _ = _run_random(kind, 1500, seed=8, rest=3, N=3, rules_kw=dict(max_screen_size=None))
+    assert L["counts"]["splits"] > 50 and m._xyz.shape[0] == L["counts"]["rows"] and torch.isfinite(m._xyz).all()
 
 
 def test_reset_opacity():
