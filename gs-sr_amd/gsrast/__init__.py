@@ -197,6 +197,7 @@ def make_cfg(variant, P, settings, D, M, render_geo, keep):
 from .mesh import cluster_connected_triangles, post_process_mesh, simplify_vertex_clustering  # noqa: E402,F401  (gsrast.mesh needs the helpers above)
 from .mesh import vertex_adjacency, compute_triangle_normals, compute_vertex_normals  # noqa: E402,F401
 from .mesh import filter_smooth_simple, filter_smooth_laplacian, filter_smooth_taubin  # noqa: E402,F401
+from .mesh import MeshRaster, rasterize_mesh, triangle_view_counts, cull_unseen_triangles  # noqa: E402,F401
 from .unbounded import extract_mesh_unbounded  # noqa: E402,F401
 from . import chamfer  # noqa: E402,F401
 from .chamfer import nearest_points, sample_surface, voxel_downsample, surface_distance  # noqa: E402,F401

@@ -197,6 +197,8 @@ FUNCTIONS = [
     ("gsr_mesh_normals", cint, [vp, i64, vp, i64, i32, vp, vp, vp, sz, vp, vp]),
     ("gsr_mesh_smooth_scratch_bytes", sz, [i64, i64, i32]),
     ("gsr_mesh_smooth", cint, [vp, vp, i64, vp, i64, i32, i32, f64, f64, i32, vp, vp, vp, sz, vp, vp]),
+    ("gsr_mesh_raster_scratch_bytes", sz, [i64, i64, i32, i32, i32]),
+    ("gsr_mesh_rasterize", cint, [vp, i64, vp, i64, vp, i32, i32, i32, f64, i32, f64, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
     ("gsr_unbounded_lattice_points", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, vp, vp, vp]),
     ("gsr_unbounded_lattice_tsdf", cint, [i32, i32, i32, vp, vp, vp, P(f32), f32, f32, i32, vp, i32, i32, vp, vp, vp, vp]),
     ("gsr_unbounded_mc_scratch_bytes", sz, [i32, i32, i32]),

@@ -11,6 +11,10 @@ of Open3D's call of that name with semantics of this project's own -- no float a
 ripple off such a mesh and give it normals (csrc/gsr_mesh_smooth.hip), again with semantics of this project's own: every sum in a
 stated order, float64 state, no float atomics.
 
+`rasterize_mesh`, `triangle_view_counts` and `cull_unseen_triangles` look at the mesh from the cameras it was fused from (csrc/gsr_mesh_raster.hip;
+DESIGN.md 4.16): depth, triangle id and barycentrics per pixel, and the triangles no camera saw taken out -- semantics of this project's own, float64
+and integer, bit-reproducible.
+
 There is no CPU path: a mesh that is not on a HIP device raises, like ScalableTSDFVolume."""
 import ctypes as C
 import math
@@ -302,6 +306,124 @@ def filter_smooth_taubin(mesh, number_of_iterations=1, lambda_filter=0.5, mu=-0.
     filter_scope; RuntimeError for a triangle index outside [0, V), a non-finite vertex, a host mesh or a mesh past V, 3T < 2^31.
     Exactly ONE host read-back per call, whatever the number of iterations: the status word, behind all the steps."""
     return _smooth(mesh, SMOOTH_TAUBIN, number_of_iterations, lambda_filter, mu, filter_scope)
+
+
+LARGE_FROM = 64                                           # candidate pixels above which a triangle is swept by a wave (DESIGN.md 4.16, the sweep)
+
+
+class MeshRaster:
+    """What rasterize_mesh returns, all device tensors: depth float32 [V,H,W] (0 where no triangle covers the pixel), triangle_id int32 [V,H,W]
+    (-1 there), barycentric float32 [V,H,W,2] or None (the perspective-correct weights of the winner's vertices 1 and 2 in the index buffer's order;
+    vertex 0 has 1 minus their sum), dropped int32 [V,3]: the triangles each view dropped as {near, guard, zero_area}."""
+
+    def __init__(self, depth, triangle_id, barycentric, dropped):
+        self.depth, self.triangle_id, self.barycentric, self.dropped = depth, triangle_id, barycentric, dropped
+
+    def interpolate(self, triangles, attr):
+        """A per-vertex attribute [n_vertices, C] at every pixel -> [V,H,W,C] of attr's dtype, 0 at empty pixels: a plain torch gather, with the
+        weights rounded to float32 (not the hot path, not bit-defined)."""
+        if self.barycentric is None:
+            raise RuntimeError("interpolate: the maps were made with want_barycentric=False")
+        if attr.dim() != 2:
+            raise RuntimeError(f"attr: expected shape [n_vertices, C] but found {list(attr.shape)}")
+        hit = self.triangle_id >= 0
+        corners = triangles.long()[self.triangle_id.clamp(min=0).long()]                     # [V,H,W,3]
+        b1, b2 = self.barycentric[..., 0:1].to(attr.dtype), self.barycentric[..., 1:2].to(attr.dtype)
+        out = (1 - b1 - b2) * attr[corners[..., 0]] + b1 * attr[corners[..., 1]] + b2 * attr[corners[..., 2]]
+        return out * hit[..., None].to(attr.dtype)
+
+    def __repr__(self):
+        return f"MeshRaster({int(self.depth.shape[0])} views, {int(self.depth.shape[2])} x {int(self.depth.shape[1])}, {self.depth.device})"
+
+
+def _raster_args(mesh, full_proj_transform, width, height, near, cull_sign, depth_tolerance=None, min_views=1):
+    """Every check of the three functions below, before the library is touched -> (vertices, triangles, matrices [n,4,4], W, H)."""
+    for name, x in (("width", width), ("height", height), ("min_views", min_views)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError(f"{name} must be a positive integer but found {x!r}")
+    if not (float(near) > 0.0) or math.isinf(float(near)):
+        raise ValueError(f"near must be a positive finite number but found {near}")
+    if isinstance(cull_sign, bool) or cull_sign not in (-1, 0, 1):
+        raise ValueError(f"cull_sign must be one of -1, 0, 1 but found {cull_sign!r}")
+    if depth_tolerance is not None and not (float(depth_tolerance) >= 0.0):
+        raise ValueError(f"depth_tolerance must be None or a non-negative number but found {depth_tolerance}")
+    if width > 16384 or height > 16384:
+        raise ValueError(f"width and height must stay within 16384 but found {width} x {height}")
+    v, _, t = _arrays(mesh)
+    m = full_proj_transform
+    if not isinstance(m, torch.Tensor):
+        raise RuntimeError("full_proj_transform must be a tensor")
+    if not m.is_cuda:
+        raise RuntimeError("full_proj_transform must be a CUDA tensor: the mesh rasterizer has no CPU path")
+    if m.dtype != torch.float32 or m.dim() not in (2, 3) or tuple(m.shape[-2:]) != (4, 4):
+        raise RuntimeError(f"full_proj_transform: expected a torch.float32 tensor of shape [4, 4] or [n, 4, 4] but found {m.dtype} {list(m.shape)}")
+    if m.device != t.device:
+        raise RuntimeError("full_proj_transform must be on the device of the mesh")
+    return v, t, m.detach().reshape(-1, 4, 4).contiguous(), int(width), int(height)
+
+
+def _rasterize(v, t, m, W, H, near, cull_sign, depth_tolerance, large_from, want_maps, want_barycentric, want_counts):
+    """One call, the one host read-back (the status word) -> (depth, triangle_id, barycentric, counts, dropped), None for what was not asked for."""
+    T, V, n, dev = int(t.shape[0]), int(v.shape[0]), int(m.shape[0]), t.device
+    nbytes = int(lib().gsr_mesh_raster_scratch_bytes(T, V, n, W, H))
+    if nbytes == 0:
+        raise _limits(T, V)
+    work = scratch(nbytes, dev)
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=dev) if want_maps else None
+    tid = torch.empty((n, H, W), dtype=torch.int32, device=dev) if want_maps else None
+    bary = torch.empty((n, H, W, 2), dtype=torch.float32, device=dev) if want_maps and want_barycentric else None
+    counts = torch.empty(T, dtype=torch.int32, device=dev) if want_counts else None
+    dropped = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    call("gsr_mesh_rasterize", dev, v if V else None, V, t if T else None, T, m if n else None, n, W, H, float(near), int(cull_sign),
+         -1.0 if depth_tolerance is None else float(depth_tolerance), int(large_from), depth, tid, bary, counts if T else None, dropped if n else None,
+         work, nbytes, status)
+    _raise_smooth_status(status.tolist()[0] & 0xFFFFFFFF)                 # the host read-back
+    return depth, tid, bary, counts, dropped
+
+
+def rasterize_mesh(mesh, full_proj_transform, width, height, near=0.01, cull_sign=0, want_barycentric=True, _large_from=LARGE_FROM):
+    """The mesh as the cameras see it -> MeshRaster(depth [V,H,W], triangle_id [V,H,W], barycentric [V,H,W,2] or None, dropped [V,3]) on the
+    mesh's device; the mesh is only read.  full_proj_transform: float32 [4,4] (one view) or [V,4,4], the reference's `Camera.full_proj_transform`
+    (row-vector convention: clip = [x y z 1] @ M); width, height: the image size of the Gaussian renderer, whose pixel grid the maps share.
+    The semantics are this project's own (include/gsrast.h, "mesh rasterization and visibility"; tests/raster_truth.py): float64
+    arithmetic, coordinates snapped to 1/256 pixel, a watertight top-left rule, per pixel the nearest covering triangle and of equally near ones the
+    one with the lowest index; no float atomics, two runs give the same bits.
+      * a triangle with a vertex at w <= near is dropped in that view, NOT clipped -- a stated departure, conservative for culling; one whose
+        snapped coordinates leave +-2^24 / 256 pixels, or whose snapped area is zero, is dropped too; dropped[v] counts the three.
+      * cull_sign=+1 / -1 keeps only the triangles whose snapped signed area2 has that sign.  -1 is the OUTSIDE of this repository's marching-cubes
+        meshes (extract_triangle_mesh: the TSDF is positive outside, the triangles counter-clockwise seen from there, signed volume > 0) under the
+        reference's camera convention (getWorld2View2 + getProjectionMatrix: +z forward, y down in the image): found on the CPU on the sphere of
+        tests/ref_mesh_numpy.py, where every triangle that owns a pixel has area2 < 0 (tests/test_raster_cpu.py).  0 rasterizes both sides.
+    Raises ValueError for width / height < 1, near <= 0 or a cull_sign outside {-1, 0, 1}; RuntimeError for host tensors, wrong dtypes or shapes,
+    a non-finite vertex and a triangle index outside [0, V).  Exactly ONE host read-back per call, whatever the number of views: the status word."""
+    v, t, m, W, H = _raster_args(mesh, full_proj_transform, width, height, near, cull_sign)
+    depth, tid, bary, _, dropped = _rasterize(v, t, m, W, H, near, cull_sign, None, _large_from, True, want_barycentric, False)
+    return MeshRaster(depth, tid, bary, dropped)
+
+
+def triangle_view_counts(mesh, full_proj_transform, width, height, near=0.01, cull_sign=0, depth_tolerance=None, _large_from=LARGE_FROM):
+    """-> counts int32 [T] on the mesh's device: in how many of the views each triangle is SEEN.  A triangle is seen in a view iff it was neither
+    dropped nor culled there (rasterize_mesh) and it owns at least one pixel of the view's triangle_id map, or -- with depth_tolerance, in the
+    units of the depth -- one of its vertices lies in the image and is no farther than the depth map at its nearest pixel plus the tolerance (or
+    that pixel is empty): a fused mesh has many triangles smaller than a pixel, which own no pixel centre and are plainly visible.  No maps are
+    kept beyond the views in flight.  Exactly ONE host read-back per call: the status word."""
+    v, t, m, W, H = _raster_args(mesh, full_proj_transform, width, height, near, cull_sign, depth_tolerance)
+    return _rasterize(v, t, m, W, H, near, cull_sign, depth_tolerance, _large_from, False, False, True)[3]
+
+
+def cull_unseen_triangles(mesh, full_proj_transform, width, height, min_views=1, depth_tolerance=None, near=0.01, cull_sign=0, return_counts=False):
+    """-> a NEW TriangleMesh without the triangles that fewer than min_views of the views see (triangle_view_counts): the back walls, interior
+    sheets and skirts of a fused TSDF that no training camera looked at and that post_process_mesh keeps because they hang on the surface.  The
+    surviving triangles keep their order, vertices no survivor references go (colours move with them); the input is left untouched and the
+    result has no normals.  With return_counts also the counts int32 [T] of the INPUT's triangles.  Two host read-backs: the status word and the
+    record of the compaction."""
+    from .tsdf import TriangleMesh
+    v, t, m, W, H = _raster_args(mesh, full_proj_transform, width, height, near, cull_sign, depth_tolerance, min_views)
+    counts = _rasterize(v, t, m, W, H, near, cull_sign, depth_tolerance, LARGE_FROM, False, False, True)[3]
+    nv, nc, tris, _ = _filter(mesh, remove_mask=(counts < int(min_views)).view(torch.uint8), flags=DROP_UNREFERENCED)
+    out = TriangleMesh(nv, nc, tris)
+    return (out, counts) if return_counts else out
 
 
 def as_remove_mask(mask, n, device):

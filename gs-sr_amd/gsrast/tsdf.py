@@ -185,6 +185,16 @@ class TriangleMesh:
         from . import mesh as _m
         return _m.filter_smooth_taubin(self, number_of_iterations, lambda_filter, mu, filter_scope)
 
+    # The mesh seen from its cameras (gsrast.mesh): both only read the mesh
+    def rasterize(self, full_proj_transform, width, height, near=0.01, cull_sign=0, want_barycentric=True):
+        from . import mesh as _m
+        return _m.rasterize_mesh(self, full_proj_transform, width, height, near, cull_sign, want_barycentric)
+
+    def cull_unseen_triangles(self, full_proj_transform, width, height, min_views=1, depth_tolerance=None, near=0.01, cull_sign=0, return_counts=False):
+        """-> a NEW mesh without the triangles that fewer than min_views views see."""
+        from . import mesh as _m
+        return _m.cull_unseen_triangles(self, full_proj_transform, width, height, min_views, depth_tolerance, near, cull_sign, return_counts)
+
     def __repr__(self):
         return f"TriangleMesh({int(self.vertices.shape[0])} vertices, {int(self.triangles.shape[0])} triangles, {self.vertices.device})"
 

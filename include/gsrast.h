@@ -713,6 +713,51 @@ size_t gsr_mesh_smooth_scratch_bytes(int64_t n_triangles, int64_t n_vertices, in
 int gsr_mesh_smooth(const float* vertices, const float* vertex_colors /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles,
                     int32_t filter, int32_t iterations, double lambda, double mu, int32_t scope, float* vertices_out, float* vertex_colors_out /*[V,3]*/,
                     void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[2]*/, void* stream);
+/* ---- mesh rasterization and visibility (no ABI bump: additions only).
+ * A mesh looked at from the cameras it was fused from: per view a depth map, a triangle-id map and perspective-correct barycentrics at the pixel grid
+ * of the Gaussian rasterizers, and per triangle the number of views that see it (what the upstream evaluation scripts cull a fused mesh with before
+ * they measure it).  The semantics are this project's own, restated operation by operation in tests/raster_truth.py.  Everything is float64 arithmetic
+ * on widened float32 inputs, each expression evaluated operation by operation in the order written, no FMA contraction; integers are exact; every
+ * output is a pure function of the inputs (no float atomics: two runs give the same bits).
+ * Inputs: vertices [V,3] float32, triangles [T,3] int32, full_proj [n_views,4,4] float32 row-major (the reference's full_proj_transform), width W,
+ * height H, near > 0 (double), cull_sign in {0, +1, -1}.
+ *   1. view: row-vector convention (compute_sdf_perframe, gssr/utils/mesh_utils.py:199-201): c_k = ((x M[0,k] + y M[1,k]) + z M[2,k]) + M[3,k];
+ *      the depth of a vertex is w = c_3.
+ *   2. pixel coordinates: ndc_x = c_0 / w, px = ((ndc_x + 1) W - 1) 0.5, likewise py with c_1 and H: the rasterizers' ndc2Pix, pixel centres at
+ *      integer coordinates.  Snapping: X = rint(px 256), Y = rint(py 256), ties to even, held as integers (1/256 pixel).
+ *   3. a triangle is DROPPED in a view and counted in dropped[view] = {near, guard, zero_area}:
+ *        near       some vertex has !(w > near).  There is NO CLIPPING -- a stated departure, conservative for culling.
+ *        guard      otherwise, some coordinate has !(|X| <= 2^24) (NaN falls here): every edge function below is then an integer below 2^52.
+ *        zero_area  otherwise, area2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) == 0.
+ *      cull_sign != 0 keeps only the triangles whose area2 has that sign; the others are culled, not counted as dropped.
+ *   4. coverage: where area2 < 0, vertices 1 and 2 are exchanged; u0, u1, u2 below are the vertices in that order, "the order of the coverage
+ *      test".  For k = 0, 1, 2 with i = (k + 1) % 3, j = (k + 2) % 3: dx = Xj - Xi, dy = Yj - Yi, E_k(P) = dx (Py - Yi) - dy (Px - Xi) at the pixel
+ *      centre P = (256 col, 256 row).  The pixel is covered iff for every k: E_k > 0, or E_k == 0 and (dy < 0 or (dy == 0 and dx > 0)) -- a
+ *      top-left rule: a centre on a shared edge belongs to exactly one of the two triangles, whatever their winding.  Candidate pixels:
+ *      ceil(Xmin / 256) .. floor(Xmax / 256) and the same in y, clamped to the image.
+ *   5. depth at a covered pixel: l_k = E_k / |area2|; iw = (l0 (1/w0) + l1 (1/w1)) + l2 (1/w2) with w_k the depth of u_k; z64 = 1 / iw;
+ *      z = (float)z64.  The winner of a pixel is the lexicographic minimum of (z as float32, triangle index) over the covering triangles.
+ *   6. outputs per view: depth [H,W] float32, the winner's z, 0 where no triangle covers (the TSDF's "no depth"); triangle_id [H,W] int32, -1 there;
+ *      barycentric [H,W,2] float32: the perspective-correct weights of the triangle's vertices 1 and 2 IN THE INDEX BUFFER'S ORDER,
+ *      (float)((l_k (1/w_k)) z64) of the u_k that is that vertex; 0 where empty.
+ *   7. visibility: a triangle is SEEN in a view iff it was neither dropped nor culled there and (a) it owns at least one pixel, or (b)
+ *      depth_tolerance >= 0 and one of its vertices passes the vertex test: fx = rint(px), fy = rint(py) lie in [0, W - 1] x [0, H - 1], compared
+ *      in float64, and that pixel is empty or w <= (double)depth[fy, fx] + depth_tolerance.  (b) is there for the triangles smaller than a pixel,
+ *      which own no centre and are plainly visible.  counts [T] int32: the number of views that see the triangle.
+ *   8. errors: a non-finite component of ANY vertex sets GSR_MESH_ERR_NONFINITE, a triangle index outside [0, V) GSR_MESH_ERR_INDEX (such a
+ *      triangle is never dereferenced), whatever the number of views; with a status the results are to be discarded.
+ *   9. limits: V < 2^31, 3T < 2^31, 1 <= W, H <= 16384; gsr_mesh_raster_scratch_bytes returns 0 beyond them.
+ * gsr_mesh_rasterize: every output may be NULL: depth_out [n_views,H,W], triangle_id_out [n_views,H,W], barycentric_out [n_views,H,W,2],
+ *   counts_out [T], dropped_out [n_views,3]; status_dev [1].  depth_tolerance < 0: no vertex test.  large_from >= 0: a triangle whose candidate box
+ *   holds more than large_from pixels is rasterized by a wave with lanes as pixels, a smaller one by one thread; the outputs do not depend on it.
+ *   Views are processed in chunks whose per-view scratch (8 H W + 5 T bytes per view) stays within 256 MiB (a chunk holds at least one view and at
+ *   most 1024); the chunks follow each other on the stream, nothing synchronises, the number of launches is a constant per chunk.  scratch:
+ *   >= gsr_mesh_raster_scratch_bytes(T, V, n_views, W, H), caller-owned.  Inputs are only read. */
+size_t gsr_mesh_raster_scratch_bytes(int64_t n_triangles, int64_t n_vertices, int32_t n_views, int32_t width, int32_t height);
+int gsr_mesh_rasterize(const float* vertices /*[V,3]*/, int64_t n_vertices, const int32_t* triangles /*[T,3]*/, int64_t n_triangles,
+                       const float* full_proj /*[n_views,16]*/, int32_t n_views, int32_t width, int32_t height, double near_plane, int32_t cull_sign,
+                       double depth_tolerance, int32_t large_from, float* depth_out, int32_t* triangle_id_out, float* barycentric_out,
+                       int32_t* counts_out, uint32_t* dropped_out, void* scratch, size_t scratch_bytes, uint32_t* status_dev /*[1]*/, void* stream);
 /* ---- the mesh of an unbounded scene (no ABI bump: additions only).
  * GaussianExtractor.extract_mesh_unbounded (gssr/utils/mesh_utils.py:181-277) over marching_cubes_with_contraction (gssr/utils/mcube_utils.py:17-95).
  * THE LATTICE.  Samples live in contracted coordinates on a dense lattice with ascending float32 axes xs[nx], ys[ny], zs[nz] (device arrays), flat
