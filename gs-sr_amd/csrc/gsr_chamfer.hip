@@ -18,6 +18,9 @@
 //               targets in chunks of 256 with their bounding boxes (k_np_gather), every box tested under the same strict rule, by the whole
 //               wave for one such query at a time (nearest box first, then whatever its best does not rule out) -- the bounded cost of a query
 //               far from everything.
+//   halves      grid, sort and table are the BUILD (gsr_np_build), into caller-owned scratch that then holds all a QUERY (gsr_np_query) reads, a sorted copy
+//               of the targets included: an ICP against a fixed scan builds once and queries per iteration (gsr_register.hip).  gsr_nearest_points is the
+//               two in a row.  A query takes a nullable device word, skip: non-zero and every workgroup returns at once, the outputs stay as they are.
 //   samples     per triangle n = max(1, ceil(sqrt(double(L2)) / spacing)), n^2 centroids; count (block scan + 64-bit total), one read-back, emit
 //               (a thread per sample: two binary searches find its triangle, an integer square root its row).
 //   thinning    key of floor(double(p) / cell), the same sort, the first of each run keeps (stable: the lowest index), keep scan in input order.
@@ -303,8 +306,11 @@ __device__ __forceinline__ unsigned long long cf_box_scan(const CfView& v, uint3
 }
 
 // No lane leaves early: the box scan at the end is the whole wave's work.
-__global__ void __launch_bounds__(CF_BLOCK) k_np_query(const float* __restrict__ query, uint32_t Q, CfView v, float md2, float* __restrict__ d2_out, int32_t* __restrict__ idx_out)
+// skip (nullable): a device word; non-zero = every workgroup returns at once and leaves its outputs alone (the launches an ICP enqueued past its stop).
+__global__ void __launch_bounds__(CF_BLOCK) k_np_query(const float* __restrict__ query, uint32_t Q, CfView v, float md2, float* __restrict__ d2_out, int32_t* __restrict__ idx_out,
+                                                       const uint32_t* __restrict__ skip)
 {
+    if (skip && *skip) return;                            // uniform over the launch
     const uint32_t qi = blockIdx.x * CF_BLOCK + threadIdx.x;
     const bool valid = qi < Q;
     float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -361,8 +367,9 @@ __global__ void __launch_bounds__(CF_BLOCK) k_np_query(const float* __restrict__
     if (valid) { d2_out[qi] = best.d2; idx_out[qi] = best.idx; }
 }
 
-__global__ void __launch_bounds__(CF_BLOCK) k_np_none(uint32_t Q, float* __restrict__ d2_out, int32_t* __restrict__ idx_out)
+__global__ void __launch_bounds__(CF_BLOCK) k_np_none(uint32_t Q, float* __restrict__ d2_out, int32_t* __restrict__ idx_out, const uint32_t* __restrict__ skip)
 {
+    if (skip && *skip) return;
     const uint32_t qi = blockIdx.x * CF_BLOCK + threadIdx.x;
     if (qi >= Q) return;
     d2_out[qi] = __uint_as_float(0x7F800000u);
@@ -392,6 +399,42 @@ static NpScratch np_carve(uint64_t T, const void* base)
 }
 static bool cf_count_ok(int64_t n) { return n >= 0 && n < (1ll << 31); }
 
+static CfView np_view(const NpScratch& m) { return CfView{ m.grid, m.nruns, m.ukey, m.ustart, m.dense, m.sorted, m.box }; }
+
+// ---- build and query (declared in gsr_common.h: gsr_register.hip builds the grid over a scan once and queries it per ICP iteration).  The scratch of
+// a build holds everything a query reads -- grid, runs, dense table, the sorted copy of the targets and their boxes -- so the target array itself is
+// not needed again.  T == 0 builds nothing and every query answers (+inf, -1).
+size_t gsr_np_scratch_bytes(uint64_t T) { return np_carve(T, nullptr).bytes; }
+
+int gsr_np_build(const char* who, const float* target, uint32_t T, float max_dist, void* scratch, hipStream_t s)
+{
+    if (T == 0) return 0;
+    const NpScratch m = np_carve((uint64_t)T, scratch);
+    const uint32_t gt = gsr_div_up(T, CF_BLOCK);
+    if (gsr_memset_async(m.bb, 0, 256, s) || gsr_memset_async(m.dense, 0, (size_t)m.dense_cap * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
+    hipLaunchKernelGGL(k_np_bbox, dim3(std::min(gsr_div_up(T, CF_BLOCK * 16u), 512u)), dim3(CF_BLOCK), 0, s, target, T, m.bb);
+    hipLaunchKernelGGL(k_np_grid, dim3(1), dim3(64), 0, s, m.bb, max_dist, m.dense_cap, m.grid);
+    hipLaunchKernelGGL(k_np_keys, dim3(gt), dim3(CF_BLOCK), 0, s, target, T, m.grid, m.key_lo, m.key_hi, m.so.ka);
+    GsrSort st(m.so);                                     // the low word, then the high word
+    if (st.sort(T, nullptr, 32, true, s) || gsr_sort_next_word(st, T, nullptr, GsrWordFromArray{m.key_hi}, s)) return 1;
+    const CfView v = np_view(m);
+    gsr_compact(CfRunOp{m.grid, st.keys, st.order, m.key_lo, m.ustart, m.ukey}, T, m.sums, m.nruns, s);
+    hipLaunchKernelGGL(k_np_dense, dim3(gt), dim3(CF_BLOCK), 0, s, v, T, m.dense_cap, m.dense);
+    hipLaunchKernelGGL(k_np_gather, dim3(gsr_div_up(T, CF_CHUNK)), dim3(CF_CHUNK), 0, s, target, T, m.grid, st.order, m.sorted, m.box);
+    return 0;
+}
+
+// the cap is the cap of the build: the cell size was chosen with it
+void gsr_np_query(const float* query, uint32_t Q, uint32_t T, float max_dist, const void* scratch, float* d2, int32_t* index, const uint32_t* skip, hipStream_t s)
+{
+    if (Q == 0) return;
+    const uint32_t gq = gsr_div_up(Q, CF_BLOCK);
+    if (T == 0) { hipLaunchKernelGGL(k_np_none, dim3(gq), dim3(CF_BLOCK), 0, s, Q, d2, index, skip); return; }
+    const NpScratch m = np_carve((uint64_t)T, scratch);
+    const float md2 = max_dist >= 0.f ? max_dist * max_dist : __builtin_inff();
+    hipLaunchKernelGGL(k_np_query, dim3(gq), dim3(CF_BLOCK), 0, s, query, Q, np_view(m), md2, d2, index, skip);
+}
+
 extern "C" size_t gsr_nearest_points_scratch_bytes(int64_t n_query, int64_t n_target)
 {
     if (!cf_count_ok(n_query) || !cf_count_ok(n_target)) return 0;
@@ -405,28 +448,42 @@ extern "C" int gsr_nearest_points(const float* query, int64_t n_query, const flo
     if (!cf_count_ok(n_query) || !cf_count_ok(n_target)) { gsr_set_error("%s: %lld queries / %lld targets out of range [0, 2^31)", who, (long long)n_query, (long long)n_target); return 1; }
     if (max_dist != max_dist) { gsr_set_error("%s: max_dist is NaN (a negative value means none)", who); return 1; }
     if ((n_query > 0 && (!query || !d2 || !index)) || (n_target > 0 && !target)) { gsr_set_error("%s: null pointer", who); return 1; }
-    const NpScratch m = np_carve((uint64_t)n_target, scratch);
-    if (gsr_scratch_check(who, scratch, scratch_bytes, m.bytes)) return 1;
+    if (gsr_scratch_check(who, scratch, scratch_bytes, np_carve((uint64_t)n_target, nullptr).bytes)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    if (n_query == 0) return 0;
-    const uint32_t Q = (uint32_t)n_query, T = (uint32_t)n_target, gq = gsr_div_up(Q, CF_BLOCK);
-    if (T == 0) {
-        hipLaunchKernelGGL(k_np_none, dim3(gq), dim3(CF_BLOCK), 0, s, Q, d2, index);
-        return gsr_check_launch(who, s, false);
-    }
-    const uint32_t gt = gsr_div_up(T, CF_BLOCK);
-    if (gsr_memset_async(m.bb, 0, 256, s) || gsr_memset_async(m.dense, 0, (size_t)m.dense_cap * 4, s)) { gsr_set_error("%s: clear", who); return 1; }
-    hipLaunchKernelGGL(k_np_bbox, dim3(std::min(gsr_div_up(T, CF_BLOCK * 16u), 512u)), dim3(CF_BLOCK), 0, s, target, T, m.bb);
-    hipLaunchKernelGGL(k_np_grid, dim3(1), dim3(64), 0, s, m.bb, max_dist, m.dense_cap, m.grid);
-    hipLaunchKernelGGL(k_np_keys, dim3(gt), dim3(CF_BLOCK), 0, s, target, T, m.grid, m.key_lo, m.key_hi, m.so.ka);
-    GsrSort st(m.so);                                     // the low word, then the high word
-    if (st.sort(T, nullptr, 32, true, s) || gsr_sort_next_word(st, T, nullptr, GsrWordFromArray{m.key_hi}, s)) return 1;
-    const CfView v = { m.grid, m.nruns, m.ukey, m.ustart, m.dense, m.sorted, m.box };
-    gsr_compact(CfRunOp{m.grid, st.keys, st.order, m.key_lo, m.ustart, m.ukey}, T, m.sums, m.nruns, s);
-    hipLaunchKernelGGL(k_np_dense, dim3(gt), dim3(CF_BLOCK), 0, s, v, T, m.dense_cap, m.dense);
-    hipLaunchKernelGGL(k_np_gather, dim3(gsr_div_up(T, CF_CHUNK)), dim3(CF_CHUNK), 0, s, target, T, m.grid, st.order, m.sorted, m.box);
-    const float md2 = max_dist >= 0.f ? max_dist * max_dist : __builtin_inff();
-    hipLaunchKernelGGL(k_np_query, dim3(gq), dim3(CF_BLOCK), 0, s, query, Q, v, md2, d2, index);
+    if (n_query == 0) return 0;                           // nobody asks: nothing is built
+    if (gsr_np_build(who, target, (uint32_t)n_target, max_dist, scratch, s)) return 1;
+    gsr_np_query(query, (uint32_t)n_query, (uint32_t)n_target, max_dist, scratch, d2, index, nullptr, s);
+    return gsr_check_launch(who, s, false);
+}
+
+extern "C" size_t gsr_nearest_grid_scratch_bytes(int64_t n_target)
+{
+    if (!cf_count_ok(n_target)) return 0;
+    return np_carve((uint64_t)n_target, nullptr).bytes;
+}
+
+extern "C" int gsr_nearest_grid_build(const float* target, int64_t n_target, float max_dist, void* scratch, size_t scratch_bytes, void* stream)
+{
+    const char* who = "nearest_grid_build";
+    if (!cf_count_ok(n_target)) { gsr_set_error("%s: %lld targets out of range [0, 2^31)", who, (long long)n_target); return 1; }
+    if (max_dist != max_dist) { gsr_set_error("%s: max_dist is NaN (a negative value means none)", who); return 1; }
+    if (n_target > 0 && !target) { gsr_set_error("%s: null pointer", who); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, np_carve((uint64_t)n_target, nullptr).bytes)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (gsr_np_build(who, target, (uint32_t)n_target, max_dist, scratch, s)) return 1;
+    return gsr_check_launch(who, s, false);
+}
+
+extern "C" int gsr_nearest_grid_query(const float* query, int64_t n_query, int64_t n_target, float max_dist, const void* scratch, size_t scratch_bytes, float* d2,
+                                      int32_t* index, const uint32_t* skip_dev, void* stream)
+{
+    const char* who = "nearest_grid_query";
+    if (!cf_count_ok(n_query) || !cf_count_ok(n_target)) { gsr_set_error("%s: %lld queries / %lld targets out of range [0, 2^31)", who, (long long)n_query, (long long)n_target); return 1; }
+    if (max_dist != max_dist) { gsr_set_error("%s: max_dist is NaN (a negative value means none)", who); return 1; }
+    if (n_query > 0 && (!query || !d2 || !index)) { gsr_set_error("%s: null pointer", who); return 1; }
+    if (gsr_scratch_check(who, scratch, scratch_bytes, np_carve((uint64_t)n_target, nullptr).bytes)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    gsr_np_query(query, (uint32_t)n_query, (uint32_t)n_target, max_dist, scratch, d2, index, skip_dev, s);
     return gsr_check_launch(who, s, false);
 }
 

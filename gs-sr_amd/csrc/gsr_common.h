@@ -205,3 +205,10 @@ void gsr_rows_keep_scan(const uint8_t* keep, uint32_t N, uint32_t* sums, uint32_
 #define GSR_SELECT_U32_DESC 1
 #define GSR_SELECT_STATE_BYTES (2 * 256 + 4 * 256 * 4)
 void gsr_select(int kind, const void* values, uint32_t n, const uint32_t* n_dev, const uint32_t rank[4], uint32_t* state, uint32_t* status, hipStream_t s);
+
+// The exact nearest-neighbour search (gsr_chamfer.hip) in its two halves: the grid over T targets built into gsr_np_scratch_bytes(T) bytes of
+// caller-owned scratch, and any number of queries against it.  max_dist is the same number for both (the cell size depends on it; < 0: none).
+// skip (nullable): a device word; while it is non-zero a query's workgroups return at once and write nothing.  Arguments are the caller's to check.
+size_t gsr_np_scratch_bytes(uint64_t T);
+int gsr_np_build(const char* who, const float* target, uint32_t T, float max_dist, void* scratch, hipStream_t s);
+void gsr_np_query(const float* query, uint32_t Q, uint32_t T, float max_dist, const void* scratch, float* d2, int32_t* index, const uint32_t* skip, hipStream_t s);

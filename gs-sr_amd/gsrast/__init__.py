@@ -201,3 +201,7 @@ from .mesh import MeshRaster, rasterize_mesh, triangle_view_counts, cull_unseen_
 from .unbounded import extract_mesh_unbounded  # noqa: E402,F401
 from . import chamfer  # noqa: E402,F401
 from .chamfer import nearest_points, sample_surface, voxel_downsample, surface_distance  # noqa: E402,F401
+from .chamfer import NearestGrid  # noqa: E402,F401
+from . import register  # noqa: E402,F401
+from .register import transform_points, correspondence_sums, solve_transform, fit_transform, icp, evaluate_registration, crop_polygon_volume  # noqa: E402,F401
+from .register import RegistrationResult  # noqa: E402,F401

@@ -234,6 +234,17 @@ FUNCTIONS = [
     ("gsr_voxel_downsample_emit", cint, [vp, i64, vp, sz, i64, vp, vp, vp]),
     ("gsr_distance_stats_scratch_bytes", sz, [i64]),
     ("gsr_distance_stats", cint, [vp, i64, f64, P(f64), i32, vp, vp, sz, vp]),
+    ("gsr_nearest_grid_scratch_bytes", sz, [i64]),
+    ("gsr_nearest_grid_build", cint, [vp, i64, f32, vp, sz, vp]),
+    ("gsr_nearest_grid_query", cint, [vp, i64, i64, f32, vp, sz, vp, vp, vp, vp]),
+    ("gsr_transform_points", cint, [vp, i64, P(f64), vp, vp]),
+    ("gsr_correspondence_sums_scratch_bytes", sz, [i64]),
+    ("gsr_correspondence_sums", cint, [vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    ("gsr_solve_transform", cint, [vp, i32, vp]),
+    ("gsr_icp_scratch_bytes", sz, [i64, i64]),
+    ("gsr_icp", cint, [vp, i64, vp, i64, f32, P(f64), i32, f64, f64, i32, vp, vp, sz, vp]),
+    ("gsr_crop_polygon_scratch_bytes", sz, []),
+    ("gsr_crop_polygon_volume", cint, [vp, i64, P(f64), i32, i32, f64, f64, vp, vp, sz, vp]),
     ("gsr_debug_read", cint, [_cfg, i32, vp, vp, sz, vp, u32, vp, vp]),
     ("gsr_profile_enable", cint, [i32]),
     ("gsr_profile_read", cint, [P(f64), P(u64)]),

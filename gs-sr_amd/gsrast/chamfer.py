@@ -4,6 +4,7 @@ tree ships no evaluation -- the 2DGS and PGSR repositories do, as host scripts o
 there: every result is DEFINED in include/gsrast.h and held to an operation-by-operation restatement (tests/chamfer_truth.py).
 
     nearest_points     exact cross-set nearest neighbour (float32 d2, lowest index among ties) through a uniform grid over the targets
+    NearestGrid        that grid built once and queried many times
     sample_surface     deterministic samples of a triangle mesh: n^2 sub-triangle centroids per triangle
     voxel_downsample   one point per occupied cell, the one with the lowest index
     surface_distance   the four figures and the F-score per threshold, float64 sums in a fixed order
@@ -73,6 +74,40 @@ def nearest_points(query, target, max_dist=None):
     work, nbytes = _scratch("gsr_nearest_points_scratch_bytes", dev, Q, T)
     call("gsr_nearest_points", dev, q if Q else None, Q, t if T else None, T, md, d2 if Q else None, index if Q else None, work, nbytes)
     return d2, index
+
+
+class NearestGrid:
+    """The search of nearest_points in its two halves: NearestGrid(target, max_dist) builds the grid over the targets once, .query(points) asks it any
+    number of times -- what an ICP against a fixed scan needs (gsrast.register).  query(q) gives the bits of nearest_points(q, target, max_dist):
+    the launches are the same.  The cap of a query is the cap of the build, because the cell size depends on it.  The grid keeps its own sorted copy
+    of the targets: the tensor handed in is not read again.  Host synchronisations: 0, build and query."""
+
+    def __init__(self, target, max_dist=None):
+        self.max_dist = _max_dist(max_dist)
+        t = _points(target, "target")
+        self.n_target, self.device = int(t.shape[0]), t.device
+        self._work, self._nbytes = _scratch("gsr_nearest_grid_scratch_bytes", self.device, self.n_target)
+        call("gsr_nearest_grid_build", self.device, t if self.n_target else None, self.n_target, self.max_dist, self._work, self._nbytes)
+
+    def query(self, points, skip=None, out=None):
+        """-> (d2 float32 [Q], index int32 [Q]) as nearest_points gives them.  skip: an int32 [1] tensor on the device; while its word is non-zero every
+        workgroup returns at once and the outputs stay as they are -- `out`, a (d2, index) pair of a former call, is then where they are."""
+        q = _points(points, "points")
+        if q.device != self.device:
+            raise RuntimeError("points must be on the device of the grid's targets")
+        Q = int(q.shape[0])
+        if out is None:
+            out = (torch.empty(Q, dtype=torch.float32, device=self.device), torch.empty(Q, dtype=torch.int32, device=self.device))
+        d2, index = out
+        if d2.dtype != torch.float32 or index.dtype != torch.int32 or tuple(d2.shape) != (Q,) or tuple(index.shape) != (Q,):
+            raise RuntimeError(f"out: expected a float32 [{Q}] and an int32 [{Q}] tensor")
+        if skip is not None and (not isinstance(skip, torch.Tensor) or skip.dtype != torch.int32 or skip.numel() != 1):
+            raise RuntimeError("skip: expected an int32 tensor of one element")
+        if Q >= 1 << 31:
+            raise RuntimeError(f"gsrast.chamfer: {Q} points out of range: every count must stay below 2^31")
+        call("gsr_nearest_grid_query", self.device, q if Q else None, Q, self.n_target, self.max_dist, self._work, self._nbytes, d2 if Q else None,
+             index if Q else None, skip)
+        return d2, index
 
 
 def _mesh_arrays(mesh):

@@ -119,6 +119,12 @@ class TriangleMesh:
     def __deepcopy__(self, memo):
         return self.clone()
 
+    def transform(self, transformation):
+        """-> a new mesh: the vertices through gsrast.register.transform_points (float64 [4,4], column-vector convention: p' = M[:3,:3] p + M[:3,3]),
+        the same triangles and colours, and no normals -- they are None after anything that moves vertices.  This mesh is left as it is."""
+        from .register import transform_points
+        return TriangleMesh(transform_points(self.vertices, transformation), self.vertex_colors, self.triangles)
+
     def has_vertex_normals(self):
         return self.vertex_normals is not None and int(self.vertex_normals.shape[0]) > 0
 

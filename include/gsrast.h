@@ -968,6 +968,95 @@ size_t gsr_distance_stats_scratch_bytes(int64_t n);
 int gsr_distance_stats(const float* d2 /*[n]*/, int64_t n, double max_dist, const double* thresholds /*host [n_thresholds]*/, int32_t n_thresholds,
                        void* record_dev /*[9 x 8 bytes]*/, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- registration: a reconstruction brought into the frame of its ground-truth scan before gsr_nearest_points / gsr_distance_stats score it -- the
+ * similarity fit of corresponding points, point-to-point ICP, the crop to a polygon volume (the Tanks-and-Temples shape of evaluation; additions, no
+ * ABI bump).  Open3D 0.18's registration_icp, TransformationEstimationPointToPoint and SelectionPolygonVolume are the model, parity with them is not
+ * pinned: every result is defined here.  Counts < 2^31, point arrays packed float32 [n,3], scratch caller-owned and 16-byte aligned, as above.
+ * A transformation is 16 doubles, row-major, in the COLUMN-vector convention: p' = M[0..2][0..2] p + M[0..2][3], bottom row (0,0,0,1) -- not the
+ * row-vector convention of gsr_cfg.projmatrix.
+ * gsr_nearest_grid_*: gsr_nearest_points in its two halves.  build: the grid over the targets into scratch (gsr_nearest_grid_scratch_bytes, the figure of
+ *   gsr_nearest_points_scratch_bytes); query: any number of times against a built scratch, with the n_target and the max_dist of the build (the cell
+ *   size depends on the cap).  gsr_nearest_points is build + query: the same launches, the same bits.  skip_dev (nullable): one device word; while it is
+ *   non-zero every workgroup of the query returns at once and d2 / index stay as they are.
+ * gsr_transform_points: out = (float)(((m00 * x + m01 * y) + m02 * z) + m03), likewise y' and z', in double on the widened input, every operation
+ *   rounded on its own; non-finite coordinates come out as the arithmetic gives them.  transformation: HOST [16], finite.
+ * gsr_correspondence_sums: over the pairs (p, q) = (source[i], target[index[i]]) with index[i] >= 0, in double: record_dev [GSR_REG_RECORD_WORDS 64-bit
+ *   words, indices GSR_REG_R_*] = {status (uint64), n (uint64), sum p [3], sum q [3], pm = sum p / n [3], qm = sum q / n [3] (0 where n == 0),
+ *   H[a][b] = sum (p - pm)_a * (q - qm)_b [9, row-major], Spp = sum ((dx*dx + dy*dy) + dz*dz) of p - pm, Sqq likewise of q - qm, M = the identity
+ *   [16], the words of gsr_icp zero}.  Two passes: the means first, the centred sums with them.  The order of the additions depends on n_source alone
+ *   (csrc/gsr_register.hip) and there are no float atomics: bit-reproducible.  index[i] == -1: no pair; any other index outside [0, n_target) sets
+ *   GSR_REG_ERR_INDEX and counts as no pair.
+ * gsr_solve_transform: from the record's n, H, Spp, Sqq, pm, qm the least-squares M with q ~ s R p + t, written to the record's M.  n < 3, Spp == 0 or
+ *   Sqq == 0: GSR_REG_ERR_DEGENERATE is set and M stays as it is.  Else, everything in double and every operation rounded on its own (Horn 1987):
+ *     A (symmetric 4x4): A00 = (H00 + H11) + H22, A11 = (H00 - H11) - H22, A22 = (H11 - H00) - H22, A33 = (H22 - H00) - H11,
+ *       A01 = H12 - H21, A02 = H20 - H02, A03 = H01 - H10, A12 = H01 + H10, A13 = H20 + H02, A23 = H12 + H21;  V = I.
+ *     Sweeps of the pairs (p,q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), until a sweep begins with all six off-diagonal elements exactly 0 or
+ *       GSR_REG_SWEEPS sweeps are done.  A pair with Apq == 0 is passed over; else
+ *         theta = (Aqq - App) / (2 * Apq);  t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta * theta + 1));  c = 1 / sqrt(t * t + 1);  s = t * c;
+ *         App -= t * Apq;  Aqq += t * Apq;  Apq = Aqp = 0;
+ *         for r = 0..3:  r != p, q:  (Arp, Arq) = (c * Arp - s * Arq, s * Arp + c * Arq), mirrored to Apr, Aqr;
+ *                        every r:    (Vrp, Vrq) = (c * Vrp - s * Vrq, s * Vrp + c * Vrq).
+ *     e = column j of V, j the index of the largest Ajj (the lowest among equal ones);  e /= sqrt(((e0*e0 + e1*e1) + e2*e2) + e3*e3);  e = -e where its
+ *       first non-zero component is negative;  (w, x, y, z) = e;
+ *     R00 = ((ww + xx) - yy) - zz, R01 = 2 (xy - wz), R02 = 2 (xz + wy), R10 = 2 (xy + wz), R11 = ((ww - xx) + yy) - zz, R12 = 2 (yz - wx),
+ *       R20 = 2 (xz - wy), R21 = 2 (yz + wx), R22 = ((ww - xx) - yy) + zz   (ww = w * w, ...): a proper rotation whatever H, no determinant fix-up.
+ *     with_scaling: s = (sum over a, then b, of Rab * Hba, added in that order from 0) / Spp and M = [s * R | qm - s * ((Ra0 pm0 + Ra1 pm1) + Ra2 pm2)];
+ *       else M = [R | qm - ((Ra0 pm0 + Ra1 pm1) + Ra2 pm2)].
+ *   Collinear pairs are NOT flagged: the rotation about their line is whatever the fixed order gives.
+ * gsr_icp: M_0 = init (HOST [16], finite); the grid over the targets built ONCE with max_dist (>= 0, finite).  Iteration k = 0, 1, ...:
+ *     P = gsr_transform_points(source, M_k) -- always of the ORIGINAL source;  (d2, index) = the query of P;  n_k = the number of index >= 0;
+ *     fitness_k = (double)n_k / n_source;  rmse_k = sqrt(sum (double)d2 / n_k) over them (0 where n_k == 0; the sum in the fixed order above);
+ *     k > 0 and |fitness_k - fitness_(k-1)| < relative_fitness and |rmse_k - rmse_(k-1)| < relative_rmse: converged, stop;
+ *     k == max_iteration: stop;
+ *     gsr_correspondence_sums(source, target, index) and gsr_solve_transform: degenerate: stop with the status, else M_(k+1) and one more iteration.
+ *   Everything is enqueued at once, 9 launches per iteration after the build; the evaluation that stops raises the record's stop word and every
+ *   later launch returns on it.  record_dev as above plus {fitness, inlier_rmse (doubles), n_inliers, iterations = solves done, converged, stop
+ *   (uint64), sum d2 (double)} of the M at the stop, which is the record's M.  The caller reads the record: its one host synchronisation.
+ * gsr_crop_polygon_volume: keep[i] = 1 iff point i is finite, axis_min <= w <= axis_max and the crossing number is odd; axis 0 / 1 / 2 = X / Y / Z is
+ *   the coordinate w, (u, v) are the other two in ascending order; polygon: HOST [n_polygon,2] doubles (u, v), finite, 3 <= n_polygon <=
+ *   GSR_REG_MAX_POLYGON.  In double, for every edge a -> b (vertex k - 1 to vertex k, cyclically) the edge is crossed iff
+ *     (a.v > v) != (b.v > v)  and  u < ((b.u - a.u) * (v - a.v)) / (b.v - a.v) + a.u
+ *   -- half-open in v, so that a vertex shared by two edges counts once.  scratch: gsr_crop_polygon_scratch_bytes(). */
+#define GSR_REG_ERR_INDEX 1u
+#define GSR_REG_ERR_DEGENERATE 2u
+#define GSR_REG_SWEEPS 32
+#define GSR_REG_MAX_POLYGON 1024
+#define GSR_REG_MAX_ITERATION 4096
+#define GSR_REG_RECORD_WORDS 48
+#define GSR_REG_R_STATUS 0
+#define GSR_REG_R_N 1
+#define GSR_REG_R_SUM_P 2
+#define GSR_REG_R_SUM_Q 5
+#define GSR_REG_R_MEAN_P 8
+#define GSR_REG_R_MEAN_Q 11
+#define GSR_REG_R_H 14
+#define GSR_REG_R_SPP 23
+#define GSR_REG_R_SQQ 24
+#define GSR_REG_R_M 25
+#define GSR_REG_R_FITNESS 41
+#define GSR_REG_R_RMSE 42
+#define GSR_REG_R_INLIERS 43
+#define GSR_REG_R_ITERATIONS 44
+#define GSR_REG_R_CONVERGED 45
+#define GSR_REG_R_STOP 46
+#define GSR_REG_R_SUM_D2 47
+size_t gsr_nearest_grid_scratch_bytes(int64_t n_target);
+int gsr_nearest_grid_build(const float* target /*[T,3]*/, int64_t n_target, float max_dist, void* scratch, size_t scratch_bytes, void* stream);
+int gsr_nearest_grid_query(const float* query /*[Q,3]*/, int64_t n_query, int64_t n_target, float max_dist, const void* scratch, size_t scratch_bytes,
+                           float* d2 /*[Q]*/, int32_t* index /*[Q]*/, const uint32_t* skip_dev /*[1] or NULL*/, void* stream);
+int gsr_transform_points(const float* points /*[N,3]*/, int64_t n_points, const double* transformation /*host [16]*/, float* out /*[N,3]*/, void* stream);
+size_t gsr_correspondence_sums_scratch_bytes(int64_t n_source);
+int gsr_correspondence_sums(const float* source /*[N,3]*/, int64_t n_source, const float* target /*[T,3]*/, int64_t n_target, const int32_t* index /*[N]*/,
+                            void* record_dev /*[48 x 8 bytes]*/, void* scratch, size_t scratch_bytes, void* stream);
+int gsr_solve_transform(void* record_dev, int32_t with_scaling, void* stream);
+size_t gsr_icp_scratch_bytes(int64_t n_source, int64_t n_target);
+int gsr_icp(const float* source /*[N,3]*/, int64_t n_source, const float* target /*[T,3]*/, int64_t n_target, float max_dist, const double* init /*host [16]*/,
+            int32_t max_iteration, double relative_fitness, double relative_rmse, int32_t with_scaling, void* record_dev /*[48 x 8 bytes]*/, void* scratch,
+            size_t scratch_bytes, void* stream);
+size_t gsr_crop_polygon_scratch_bytes(void);
+int gsr_crop_polygon_volume(const float* points /*[N,3]*/, int64_t n_points, const double* polygon /*host [K,2]*/, int32_t n_polygon, int32_t axis, double axis_min,
+                            double axis_max, uint8_t* keep /*[N]*/, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
