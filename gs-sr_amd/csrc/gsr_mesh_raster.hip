@@ -260,10 +260,11 @@ struct RsScratch {
     uint8_t* owner;                               // [chunk][T]
     uint32_t chunk; size_t bytes;
 };
+// 3V as well as 3T: k_rs_check takes one thread per vertex component and index, and its grid rounds 3 max(V, T) up in 32 bits
 static bool rs_sizes_ok(int64_t T, int64_t V, int64_t n_views, int64_t W, int64_t H)
 {
-    return T >= 0 && V >= 0 && V <= 0x7FFFFFFFll && 3 * (unsigned long long)T < (1ull << 31) && n_views >= 0 && n_views <= 0x7FFFFFFFll && W >= 1 && H >= 1 &&
-           W <= RS_DIM_MAX && H <= RS_DIM_MAX;
+    return T >= 0 && V >= 0 && V <= 0x7FFFFFFFll && 3 * (unsigned long long)V < (1ull << 31) && T <= 0x7FFFFFFFll && 3 * (unsigned long long)T < (1ull << 31) &&
+           n_views >= 0 && n_views <= 0x7FFFFFFFll && W >= 1 && H >= 1 && W <= RS_DIM_MAX && H <= RS_DIM_MAX;
 }
 static RsScratch rs_carve(uint64_t T, uint64_t n_views, uint64_t HW, const void* base)
 {
@@ -295,7 +296,7 @@ extern "C" int gsr_mesh_rasterize(const float* vertices, int64_t n_vertices, con
 {
     const char* who = "mesh_rasterize";
     if (!rs_sizes_ok(n_triangles, n_vertices, n_views, width, height)) {
-        gsr_set_error("%s: %lld triangles / %lld vertices / %d views at %d x %d out of range: V and 3T must stay below 2^31, width and height within [1, %d]", who,
+        gsr_set_error("%s: %lld triangles / %lld vertices / %d views at %d x %d out of range: 3V and 3T must stay below 2^31, width and height within [1, %d]", who,
                       (long long)n_triangles, (long long)n_vertices, n_views, width, height, RS_DIM_MAX);
         return 1;
     }

@@ -281,7 +281,13 @@ struct SmScratch {
     size_t bytes;
 };
 static int sm_bits(uint64_t V) { int b = 1; while (b < 32 && (1ull << b) <= V) b++; return b; }        // the keys are 0 .. V
-static bool sm_sizes_ok(int64_t T, int64_t V) { return T >= 0 && V >= 0 && V <= 0x7FFFFFFFll && 3 * (unsigned long long)T < (1ull << 31); }
+// The 6T pairs go through kernels, the sort and the compaction, whose grids and block counts round their number up in 32 bits, by up to
+// SM_SIZE_SLACK (the sort's largest block, GSR_SORT_THREADS * 16): 6T + SM_SIZE_SLACK <= 2^32, a few hundred triangles short of 3T < 2^31.
+#define SM_SIZE_SLACK 4096ull
+static bool sm_sizes_ok(int64_t T, int64_t V)
+{
+    return T >= 0 && V >= 0 && V <= 0x7FFFFFFFll && T <= 0x7FFFFFFFll && 6 * (unsigned long long)T + SM_SIZE_SLACK <= (1ull << 32);
+}
 static uint32_t sm_grid(uint32_t n) { return gsr_div_up(n > 0 ? n : 1u, SM_BLOCK); }
 // per_tri: the elements of the sort per triangle (6 pairs or 3 corners); starts: the V + 1 words; channels: doubles per state row (0: no state)
 static SmScratch sm_carve(uint64_t T, uint64_t V, int per_tri, bool starts, int channels, const void* base)
@@ -344,7 +350,7 @@ extern "C" size_t gsr_mesh_smooth_scratch_bytes(int64_t n_triangles, int64_t n_v
 static int sm_sizes(const char* who, int64_t T, int64_t V)
 {
     if (sm_sizes_ok(T, V)) return 0;
-    gsr_set_error("%s: %lld triangles / %lld vertices out of range: V and 3T must stay below 2^31", who, (long long)T, (long long)V);
+    gsr_set_error("%s: %lld triangles / %lld vertices out of range: V must stay below 2^31 and 6T within 2^32 - 4096", who, (long long)T, (long long)V);
     return 1;
 }
 

@@ -189,8 +189,8 @@ SMOOTH_SIMPLE, SMOOTH_LAPLACIAN, SMOOTH_TAUBIN = 0, 1, 2    # GSR_SMOOTH_*
 SCOPES = {"all": 0, "vertex": 1}                           # GSR_SMOOTH_SCOPE_*
 
 
-def _limits(T, V):
-    return RuntimeError(f"mesh: {T} triangles / {V} vertices: V and 3T must stay below 2^31; process the mesh in parts")
+def _limits(T, V, rule="V must stay below 2^31 and 6T within 2^32 - 4096"):
+    return RuntimeError(f"mesh: {T} triangles / {V} vertices: {rule}; process the mesh in parts")
 
 
 def _raise_smooth_status(status):
@@ -303,7 +303,7 @@ def filter_smooth_taubin(mesh, number_of_iterations=1, lambda_filter=0.5, mu=-0.
       * number_of_iterations=0 returns a copy, bit for bit.  The new mesh has a copy of the input's triangles and NO normals: compute_vertex_normals
         is one call.
     Raises ValueError before any launch for a negative or non-integer number_of_iterations, a non-finite lambda_filter / mu or an unknown
-    filter_scope; RuntimeError for a triangle index outside [0, V), a non-finite vertex, a host mesh or a mesh past V, 3T < 2^31.
+    filter_scope; RuntimeError for a triangle index outside [0, V), a non-finite vertex, a host mesh or a mesh past V < 2^31, 6T <= 2^32 - 4096.
     Exactly ONE host read-back per call, whatever the number of iterations: the status word, behind all the steps."""
     return _smooth(mesh, SMOOTH_TAUBIN, number_of_iterations, lambda_filter, mu, filter_scope)
 
@@ -367,7 +367,7 @@ def _rasterize(v, t, m, W, H, near, cull_sign, depth_tolerance, large_from, want
     T, V, n, dev = int(t.shape[0]), int(v.shape[0]), int(m.shape[0]), t.device
     nbytes = int(lib().gsr_mesh_raster_scratch_bytes(T, V, n, W, H))
     if nbytes == 0:
-        raise _limits(T, V)
+        raise _limits(T, V, "3V and 3T must stay below 2^31")
     work = scratch(nbytes, dev)
     depth = torch.empty((n, H, W), dtype=torch.float32, device=dev) if want_maps else None
     tid = torch.empty((n, H, W), dtype=torch.int32, device=dev) if want_maps else None

@@ -665,8 +665,9 @@ int gsr_mesh_simplify_emit(const float* vertices, const float* vertex_colors /*[
  * on the mesh post_process_mesh and the simplification leave.  Open3D 0.18's published sources are the model (area-weighted vertex normals,
  * inverse-distance Laplacian weights, the (0, 0, 1) fallback) but Open3D is not part of the reference tree and PARITY IS UNPINNED: the semantics
  * below are this project's own, stated so that every result is deterministic (no float atomics: two runs give the same bits), and restated operation
- * by operation in tests/smooth_truth.py.  Mesh: vertices [V,3] float32, vertex_colors [V,3] float32, triangles [T,3] int32; V < 2^31 and 3T < 2^31,
- * every *_scratch_bytes function below returns 0 beyond that (and for an unknown scope).
+ * by operation in tests/smooth_truth.py.  Mesh: vertices [V,3] float32, vertex_colors [V,3] float32, triangles [T,3] int32; V < 2^31 and 6T <= 2^32 - 4096
+ * (the 6T vertex pairs are counted, with the rounding of their grids, in 32 bits), every *_scratch_bytes function below returns 0 beyond that (and for an
+ * unknown scope).
  *   1. adjacency: N(i) = the set of j != i that share at least one triangle with i, distinct and ascending.  A triangle with two equal indices
  *      adds no self-loop and still connects its two distinct vertices.  A triangle index outside [0, V) sets GSR_MESH_ERR_INDEX; nothing is
  *      dereferenced through it and its triangle connects nothing.  The result is a CSR: start int32 [V + 1], neighbours int32 [E],
@@ -746,7 +747,7 @@ int gsr_mesh_smooth(const float* vertices, const float* vertex_colors /*[V,3]*/,
  *      which own no centre and are plainly visible.  counts [T] int32: the number of views that see the triangle.
  *   8. errors: a non-finite component of ANY vertex sets GSR_MESH_ERR_NONFINITE, a triangle index outside [0, V) GSR_MESH_ERR_INDEX (such a
  *      triangle is never dereferenced), whatever the number of views; with a status the results are to be discarded.
- *   9. limits: V < 2^31, 3T < 2^31, 1 <= W, H <= 16384; gsr_mesh_raster_scratch_bytes returns 0 beyond them.
+ *   9. limits: 3V < 2^31, 3T < 2^31, 1 <= W, H <= 16384; gsr_mesh_raster_scratch_bytes returns 0 beyond them.
  * gsr_mesh_rasterize: every output may be NULL: depth_out [n_views,H,W], triangle_id_out [n_views,H,W], barycentric_out [n_views,H,W,2],
  *   counts_out [T], dropped_out [n_views,3]; status_dev [1].  depth_tolerance < 0: no vertex test.  large_from >= 0: a triangle whose candidate box
  *   holds more than large_from pixels is rasterized by a wave with lanes as pixels, a smaller one by one thread; the outputs do not depend on it.

@@ -41,6 +41,20 @@ def two_clusters():
     return a3(q), a3(c)
 
 
+def ring(n):
+    """n targets on the unit circle of the plane z = 0, (cos, sin, 0) of 2 pi k / n rounded to float32: the box is [-1,1] x [-1,1], the cell rule gives
+    h = sqrt(4 / n) and floor(2 / h) + 1 cells along x and y -- a dense table whose middle is empty.  From the centre every target is within a few
+    ulps of d2 = 1 and many d2 are equal: the lowest index among the smallest has to survive."""
+    a = 2.0 * np.pi * np.arange(n) / n
+    return a3(np.stack([np.cos(a), np.sin(a), np.zeros(n)], 1))
+
+
+RING_QUERIES = a3([[0, 0, 0], [0.05, -0.02, 0], [0.3, 0.1, 0],      # the centre and near it: the shells of the dense table run out, the box scan answers
+                   [0.97, 0.05, 0], [-0.6, -0.78, 0]])             # just inside the rim: answered within the shells
+Q_RING_CENTRE, Q_RING_RIM = 0, (3, 4)
+Q_RING_FAR = {"ring_400": (0, 1), "ring_1024": (0, 1, 2)}          # the queries whose nearest target is more than CF_RINGS shells away
+
+
 def _clustered(seed, n):
     """A 100:1 density contrast: half of the points in the unit cube, half in a cube of a hundredth of its volume."""
     r = np.random.default_rng(seed)
@@ -85,6 +99,8 @@ def _build():
     off = F(1e4)
     c["offset_1e4"] = (off + _u(14, 300, 0, 0.02), off + _u(15, 300, 0, 0.02), None)       # an ulp at 1e4 is 9.8e-4: a few ulps of structure
     c["two_clusters"] = two_clusters() + (None,)
+    c["ring_400"] = (RING_QUERIES, ring(400), None)                                       # 21 x 21 x 1 cells, 2 chunks of the box scan
+    c["ring_1024"] = (RING_QUERIES, ring(1024), None)                                     # 33 x 33 x 1 cells, 4 chunks
     q, t = _nonfinite()
     c["nonfinite"] = (q, t, None)
     c["nonfinite_capped"] = (q, t, 0.1)
@@ -116,6 +132,17 @@ def random_mesh(T, seed=41):
     return a3(r.uniform(-1, 1, (40, 3))), r.integers(0, 40, (T, 3)).astype(np.int32), 0.6
 
 
+def uneven_mesh():
+    """2048 triangles, spacing 0.6: the first 1024 inside a cube of edge 0.3 (n = 1, one sample each), the next 1024 with an edge from a cluster at
+    x = +1.6 to one at x = -1.6 (n >= 5, 25 samples or more each): the sums of the two blocks of 1024 triangles differ by more than 25 times."""
+    r = np.random.default_rng(43)
+    v = np.concatenate([r.uniform(-0.15, 0.15, (20, 3)), r.uniform(-0.15, 0.15, (10, 3)) + [1.6, 0, 0], r.uniform(-0.15, 0.15, (10, 3)) - [1.6, 0, 0]])
+    small = r.integers(0, 20, (1024, 3))
+    wide = np.stack([r.integers(20, 30, 1024), r.integers(30, 40, 1024), r.integers(0, 40, 1024)], 1)
+    return a3(v), np.concatenate([small, wide]).astype(np.int32), 0.6
+
+
+SAMPLER_BLOCK = 1024                                      # csrc/gsr_chamfer.hip SS_BLOCK: triangles per workgroup of the count, one scanned sum each
 MESHES = {
     "edge_exactly_3_spacings": _mesh(TRI, [[0, 1, 2]], 1.0),                                         # n = 3
     "edge_exactly_4_spacings": _mesh(TRI, [[0, 1, 2]], 0.75),                                        # n = 4
@@ -128,8 +155,14 @@ MESHES = {
     "n17": _mesh([[0, 0, 0], [17, 0, 0], [3, 5, 1]], [[0, 1, 2]], 1.0),
     "T1": random_mesh(1),
     "T65": random_mesh(65),
+    "T1023": random_mesh(1023),                                                                      # one block of the sampler, one short of full
+    "T1024": random_mesh(1024),                                                                      # one full block
+    "T1025": random_mesh(1025),                                                                      # a second block of one triangle
+    "T3077": random_mesh(3077),                                                                      # four blocks, the last partial
+    "T2048_uneven": uneven_mesh(),
     "two_triangles": _mesh([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], [[0, 1, 2], [0, 2, 3]], 0.3),
 }
+MESH_BLOCKS = {"T1023": 1, "T1024": 1, "T1025": 2, "T3077": 4, "T2048_uneven": 2}
 MESH_N = {"edge_exactly_3_spacings": 3, "edge_exactly_4_spacings": 4, "edge_one_ulp_above": 4, "all_equal": 1, "n1": 1, "n2": 2, "n3": 3, "n17": 17}
 MESH_BAD_INDEX = _mesh(TRI, [[0, 1, 2], [0, 1, 3]], 1.0)
 MESH_NEGATIVE_INDEX = _mesh(TRI, [[0, -1, 2]], 1.0)

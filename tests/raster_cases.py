@@ -1,5 +1,5 @@
 """Named inputs for the tests of the mesh rasterizer: CASES[name] = dict(v float32 [V,3], c float32 [V,3], t int32 [T,3], mats float32 [n,4,4],
-W, H, near, cull_sign).  Every case is small -- 6400 triangles and 128 x 96 at most -- and the truths (tests/raster_truth.py) are computed once per
+W, H, near, cull_sign).  Every case is small -- 6400 triangles and 128 x 96 at most, the one with 1030 views 12 triangles at 16 x 12 -- and the truths (tests/raster_truth.py) are computed once per
 case and shared (truth()), their arrays read-only.
 
 Two kinds of matrices:
@@ -138,8 +138,7 @@ def _all():
     return c
 
 
-CASES = _all()
-NAMES = sorted(CASES)
+CASES = _all()                                            # box_1030_views joins below, NAMES follows it
 SPHERES = ("sphere_33x31", "sphere_64x48", "sphere_128x96")
 TOLERANCE = 0.05                                          # depth_tolerance of the visibility tests, in the units of the spheres (radius 1)
 
@@ -209,3 +208,10 @@ def closed_box():
     normals = np.repeat(np.array([(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)], np.float64), 2, axis=0)
     eyes = np.array([(3, 0, 0), (-3, 0, 0), (0, 3, 0), (0, -3, 0), (0.01, 0.02, 3), (0.02, 0.01, -3)], np.float64)
     return _case(v, t, np.stack([camera(e) for e in eyes]), 48, 36), normals, eyes
+
+
+# The box from 1030 cameras around it at 16 x 12: more views than one chunk of the rasterizer takes (MANY_VIEWS > CHUNK_MAX, csrc/gsr_mesh_raster.hip
+# RS_CHUNK_MAX; test_raster_cpu holds the chunk rule), so the views from 1024 on go through a second turn of its loop.
+CHUNK_MAX, MANY_VIEWS = 1024, 1030
+CASES["box_1030_views"] = _case(closed_box()[0]["v"], closed_box()[0]["t"], ring(MANY_VIEWS), 16, 12, seed=6)
+NAMES = sorted(CASES)

@@ -106,6 +106,41 @@ def units_from_dense(tsdf, weight, color, origin_unit):
     return np.array(co, np.int32), np.stack(T), np.stack(W), np.stack(Cc)
 
 
+def field_unit(rng):
+    """One unit of a random field: tsdf in (-1, 1) with 1 % exact zeros, 10 % of the voxels without weight, random colours.  -> (tsdf, weight, color)"""
+    f = rng.uniform(-1, 1, (16, 16, 16)).astype(np.float32)
+    f[rng.uniform(size=(16, 16, 16)) < 0.01] = 0.0
+    w = ((rng.uniform(size=(16, 16, 16)) > 0.1) * rng.integers(1, 9, (16, 16, 16))).astype(np.float32)
+    return f, w, rng.uniform(0, 255, (16, 16, 16, 3)).astype(np.float32)
+
+
+def row_units(fields, units):
+    """Unit lists (coords, tsdf, weight, color) of the given units of a row along x: `fields` {unit: field_unit()}, every other unit the filler
+    tsdf 0.5 at weight 1 -- present, live, without a surface of its own, but with one against a field unit beside it."""
+    units = np.asarray(units, np.int64)
+    n = len(units)
+    T, W, Cc = np.full((n, 16, 16, 16), 0.5, np.float32), np.ones((n, 16, 16, 16), np.float32), np.zeros((n, 16, 16, 16, 3), np.float32)
+    for k, u in enumerate(units.tolist()):
+        if u in fields:
+            T[k], W[k], Cc[k] = fields[u]
+    co = np.zeros((n, 3), np.int32)
+    co[:, 0] = units
+    return co, T, W, Cc
+
+
+def extract_row(fields, lo, hi, voxel_length):
+    """extract() of units lo .. hi - 1 of the row alone, at their place."""
+    T, W, Cc, org = dense_from_units(*row_units(fields, np.arange(lo, hi)))
+    return extract(T, W, Cc, voxel_length, origin=org)
+
+
+def concat(meshes):
+    """Meshes that share no vertex, one after the other: the triangles of each offset by the vertices in front of it."""
+    base = np.cumsum([0] + [len(m[0]) for m in meshes[:-1]])
+    return (np.concatenate([m[0] for m in meshes]), np.concatenate([m[1] for m in meshes]),
+            np.concatenate([m[2] + np.int32(b) for m, b in zip(meshes, base)]).astype(np.int32))
+
+
 def topology(triangles, n_vertices):
     """-> dict(watertight, euler, unused): every directed edge has its opposite exactly once; V - E + F; vertices no triangle names."""
     t = np.asarray(triangles, np.int64)

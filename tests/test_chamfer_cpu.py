@@ -2,6 +2,7 @@
 named cases of tests/chamfer_cases.py rest on (under the documented cell rule), and what can be held without a GPU of the binding: the exports, the
 ABI version, the host-side argument errors."""
 import math
+import os
 import re
 
 import numpy as np
@@ -11,6 +12,7 @@ import chamfer_cases as cases
 import chamfer_truth as truth
 
 F = np.float32
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gs-sr_amd", "csrc")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the truth, by hand
@@ -88,6 +90,24 @@ def test_sampler_case_structure():
     v, t, s = cases.MESHES["T65"]
     ns = [truth.triangle_n(v[a], v[b], v[c], s) for a, b, c in t]
     assert min(ns) >= 1 and max(ns) >= 3 and len(set(ns)) >= 3                  # the block scan meets different counts
+    # more than one block of the sampler: the count writes one sum per SS_BLOCK triangles, the emit searches their scanned sums first
+    B = cases.SAMPLER_BLOCK
+    src = open(os.path.join(CSRC, "gsr_chamfer.hip")).read()
+    assert re.search(r"^#define SS_BLOCK %d\s" % B, src, flags=re.M) and "gsr_div_up(a.T, SS_BLOCK)" in src
+    for name, blocks in cases.MESH_BLOCKS.items():
+        v, t, s = cases.MESHES[name]
+        ns = np.array([truth.triangle_n(v[a], v[b], v[c], s) for a, b, c in t])
+        assert -(-len(t) // B) == blocks and (blocks > 1) == (len(t) > B), name
+        sums = [int((ns[k * B:(k + 1) * B] ** 2).sum()) for k in range(blocks)]
+        prefix = np.cumsum([0] + sums)
+        p = truth.sample_surface(v, t, s)
+        assert len(p) == prefix[-1] and min(sums) >= 1, name
+        for k in range(1, blocks):                                              # sample prefix[k] exists and is the first of block k's first triangle
+            assert prefix[k] < len(p) and np.array_equal(p[prefix[k]], truth.sample_surface(v, t[k * B:k * B + 1], s)[0]), (name, k)
+            assert not np.array_equal(p[prefix[k]], p[prefix[k] - 1])
+        if name == "T2048_uneven":
+            assert (ns[:B] == 1).all() and ns[B:].min() >= 5 and sums[0] == B and sums[1] >= 25 * B
+    assert len(truth.sample_surface(*cases.MESHES["T3077"])) == 33324
 
 
 def test_samples_are_sub_triangle_centroids_of_equal_weight():
@@ -168,6 +188,31 @@ def test_two_clusters_force_the_sparse_table():
     assert c[100:, 0].min() - c[:100, 0].max() >= 99000 and abs(g["h"] - 0.01) < 1e-4
     mid = truth.cell_of(g, q[29])                                              # (500, 0, 0)
     assert np.abs(c - mid).max(axis=1).min() > truth.RINGS                     # its shells run out: the box scan answers
+
+
+@pytest.mark.parametrize("name,cells,chunks", [("ring_400", 21, 2), ("ring_1024", 33, 4)])
+def test_rings_leave_the_dense_table_for_the_box_scan(name, cells, chunks):
+    """k_np_query walks shells 0..CF_RINGS of the dense table and then falls back to cf_box_scan: the queries named in Q_RING_FAR find every one of
+    those shells empty, the rim queries are answered inside them."""
+    src = open(os.path.join(CSRC, "gsr_chamfer.hip")).read()
+    assert re.search(r"^#define CF_RINGS %d\s" % truth.RINGS, src, flags=re.M) and re.search(r"^#define CF_CHUNK 256\s", src, flags=re.M)
+    q, t, m = cases.NEAREST[name]
+    assert m is None and q is cases.RING_QUERIES
+    g = truth.grid_rule(t)
+    assert g["dense"] and g["n"].tolist() == [cells, cells, 1] and -(-g["Tf"] // 256) == chunks
+    c = truth.cell_of(g, t)
+    shell = lambda k: int(np.abs(c - truth.cell_of(g, q[k])).max(axis=1).min())
+    for k in cases.Q_RING_FAR[name]:
+        assert shell(k) > truth.RINGS, (name, k, shell(k))
+        assert truth.RINGS + 1 <= truth.cell_of(g, q[k])[0] < cells - truth.RINGS - 1         # the grid goes on beyond the last shell: the walk does not end for lack of cells
+    assert cases.Q_RING_CENTRE in cases.Q_RING_FAR[name]
+    for k in cases.Q_RING_RIM:
+        assert shell(k) <= truth.RINGS, (name, k, shell(k))
+    d = truth.pair_d2(q[cases.Q_RING_CENTRE][None], t)[0]
+    d2, i = truth.nearest(q, t)
+    assert (d == d.min()).sum() >= 2 and d2[cases.Q_RING_CENTRE] == d.min() and i[cases.Q_RING_CENTRE] == np.flatnonzero(d == d.min())[0]
+    assert np.abs(d.astype(np.float64) - 1.0).max() <= 4 * 2.0 ** -24 and len(np.unique(d)) >= 2     # every target within a few ulps of d2 = 1, not all equal
+    assert (i >= 0).all()
 
 
 def test_far_and_cap_case_structure():

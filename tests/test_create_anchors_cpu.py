@@ -117,6 +117,29 @@ def test_argument_errors_without_a_device():
     assert "int32" in init.status_message("x", 2) and "non-finite" in init.status_message("x", 1)
 
 
+def test_the_quantile_case_past_the_block_cap_makes_a_workgroup_take_a_second_chunk():
+    """k_cq_hist's grid is (min(chunks, max(1, CQ_BLOCKS / batches)), batches) and a workgroup walks chunk = blockIdx.x, += gridDim.x: the loop turns
+    a second time only where the chunks outnumber grid.x.  The constants the GPU tests mirror are the source's, and the case crosses the cap with a
+    partial last batch and a partial last chunk."""
+    import test_gpu_create_anchors as G
+    src = open(os.path.join(ROOT, "gs-sr_amd", "csrc", "gsr_init.hip")).read()
+    define = lambda name: re.search(r"^#define %s\s+(\S+(?: \* \S+\))?)" % name, src, flags=re.M).group(1)
+    assert define("CQ_CB") == str(G.BATCH) and define("CQ_BLOCKS") == f"{G.BLOCKS}u"
+    assert define("CQ_CHUNK") == "(SEL_BLOCK * CQ_PPT)" and int(define("SEL_BLOCK")) * int(define("CQ_PPT")) == G.CHUNK
+    assert "std::min(gsr_div_up((uint32_t)N, CQ_CHUNK), std::max(1u, CQ_BLOCKS / batches)), batches)" in src and "chunk += gridDim.x" in src
+    div_up = lambda a, b: -(-a // b)
+    grid_x = lambda C, N: min(div_up(N, G.CHUNK), max(1, G.BLOCKS // div_up(C, G.BATCH)))
+    make_p, make_c, r = G.QUANTILE_CASES["past_the_block_cap"]
+    C, N = make_c().shape[0], make_p().shape[0]
+    assert (C, N) == G.PAST_CAP and r == 0.999
+    assert div_up(N, G.CHUNK) > max(1, G.BLOCKS // div_up(C, G.BATCH)) and C % G.BATCH != 0 and N % G.CHUNK != 0
+    assert (div_up(C, G.BATCH), grid_x(C, N), div_up(N, G.CHUNK), C % G.BATCH, N % G.CHUNK) == (512, 8, 10, 2, 5)
+    assert len(set(make_c()[:, 3].tolist())) == 4                                             # cameras of mixed scales
+    for name, (mp, mc, _) in G.QUANTILE_CASES.items():                                        # no other case gets there
+        if name != "past_the_block_cap":
+            assert grid_x(mc().shape[0], mp().shape[0]) == div_up(mp().shape[0], G.CHUNK), name
+
+
 def _lerp_fused(a, b, w):
     a, b, w = np.float32(a), np.float32(b), np.float32(w)
     d = np.float64(np.float32(b - a))                       # the product of two float32 is exact in float64; the one rounding to float32 follows

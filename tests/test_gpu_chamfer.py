@@ -41,8 +41,11 @@ def test_nearest_points(name):
     _same(_nearest(q, t, m), truth.nearest(q, t, m), name)
 
 
-@pytest.mark.parametrize("name", ["lattice", "far_query", "two_clusters", "offset_1e4", "size_Q257_T257"])
-@pytest.mark.parametrize("m", [0.05, 0.75, 3.0])
+CAPPED = ([(m, name) for name in ("lattice", "far_query", "two_clusters", "offset_1e4", "size_Q257_T257") for m in (0.05, 0.75, 3.0)] +
+          [(m, name) for name in ("ring_400", "ring_1024") for m in (0.5, 0.999, 1.5)])      # the rings: short of the rim, just short of it, beyond it
+
+
+@pytest.mark.parametrize("m,name", CAPPED)
 def test_nearest_points_with_a_cap(name, m):
     """The cases that carry no cap of their own, under three: the cap clamps the cell size from below and ends the shells early."""
     q, t, _ = cases.NEAREST[name]
@@ -205,6 +208,17 @@ def _big_stats(m, taus):
     f = [(2.0 * p * r / (p + r) if p + r > 0 else 0.0) for p, r in zip(P, R)]
     return {"accuracy": acc, "completeness": comp, "chamfer": 0.5 * (acc + comp), "thresholds": [float(t) for t in taus], "precision": P, "recall": R,
             "fscore": f, "n_pred": 20000, "n_gt": 20000}
+
+
+def test_surface_distance_of_a_mesh_of_four_sampler_blocks():
+    """T3077: the samples of a mesh of more than 1024 triangles (four blocks of the sampler's count, 33 324 samples) go through the whole chain."""
+    from gsrast import chamfer
+    v, t, s = cases.MESHES["T3077"]
+    cloud = cases.NEAREST["size_Q257_T257"][1]
+    taus = (0.05, 0.2, 0.5)
+    want = truth.surface_distance(truth.sample_surface(v, t, s), cloud, None, taus)
+    assert want["n_pred"] == 33324 and 0 < want["precision"][0] < want["precision"][2] < 1
+    _check_stats(chamfer.surface_distance(_Mesh(v, t), _dev(cloud), spacing=s, thresholds=taus), want)
 
 
 def test_mesh_against_its_own_samples():

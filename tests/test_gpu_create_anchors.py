@@ -2,7 +2,8 @@
 Everything is compared by exact equality: whole calls against the fixtures the reference's own create_from_data produced
 (tests/golden/make_golden_create_anchors.py, whose margins keep that honest), the pieces against torch / numpy on the CPU from the same float32
 inputs -- torch.quantile per camera (its order statistics, then ATen's Lerp.h operation by operation: _quantile_cpu), torch.kthvalue, torch.unique(dim=0), np.unique(axis=0) -- at the sizes where the kernels change path: around the
-2048-point chunk of a workgroup, one camera past the batch of 8, around the 1024-key sort block, one element and one level."""
+2048-point chunk of a workgroup, one camera past the batch of 8, more chunks than a camera batch has workgroups, around the 1024-key sort block, one
+element and one level."""
 import glob
 import os
 import types
@@ -20,6 +21,7 @@ SCAFFOLD = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "r
 DEV = "cuda:0"
 MODES = ("floor", "round", "ceil")
 CHUNK, BATCH, SORT_BLOCK = 2048, 8, 1024          # csrc/gsr_init.hip CQ_CHUNK, CQ_CB; csrc/gsr_common.h GSR_SORT_BLOCK
+BLOCKS = 4096                                     # csrc/gsr_init.hip CQ_BLOCKS: a camera batch gets max(1, BLOCKS // batches) workgroups for its point chunks
 
 
 def _inverse_sigmoid(x):
@@ -165,7 +167,18 @@ QUANTILE_CASES = {
     "two_clusters": (lambda: _clusters(5000), lambda: torch.tensor([[0.0, 0.0, 0.0, 1.0], [100.0, 100.0, 100.0, 3.0], [50.0, 50.0, 50.0, 1.0]]), 0.999),
     "ratio_one": (lambda: _cloud(2500, 13), lambda: _cams(3, 13), 1.0),
     "ratio_half": (lambda: _cloud(2500, 14), lambda: _cams(3, 14, (2.0,)), 0.5),
+    # 512 camera batches (the last of 2 cameras) leave 4096 // 512 = 8 workgroups to a batch's 10 point chunks (the last of 5 points): workgroups 0 and 1
+    # take a second chunk into the same LDS histograms (test_create_anchors_cpu holds the three inequalities)
+    "past_the_block_cap": (lambda: _cloud(PAST_CAP[1], 15), lambda: _cams(PAST_CAP[0], 15, (1.0, 2.0, 0.5, 4.0)), 0.999),
 }
+PAST_CAP = (4090, 9 * CHUNK + 5)                  # cameras, points
+
+
+def _quantiles_cpu_in_parallel(points, cams, r, block=50, workers=8):
+    """_quantiles_cpu itself over blocks of cameras, on a few threads: a camera's two numbers depend on no other camera."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(workers) as ex:
+        return torch.cat(list(ex.map(lambda i: _quantiles_cpu(points, cams[i:i + block], r), range(0, cams.shape[0], block))))
 
 
 @pytest.mark.parametrize("case", sorted(QUANTILE_CASES))
@@ -173,7 +186,7 @@ def test_camera_dist_quantiles_equal_torch_quantile(case):
     from gsrast import init
     make_p, make_c, r = QUANTILE_CASES[case]
     p, c = make_p(), make_c()
-    want = _quantiles_cpu(p, c, r)
+    want = _quantiles_cpu(p, c, r) if c.shape[0] <= 64 else _quantiles_cpu_in_parallel(p, c, r)
     got = init.camera_dist_quantiles(p.to(DEV), c.to(DEV), r)
     assert got.dtype == torch.float32 and tuple(got.shape) == (2 * c.shape[0],)
     assert torch.equal(got.cpu(), want), (case, (got.cpu() - want).abs().max())

@@ -136,6 +136,43 @@ def test_more_than_1024_units():
     _check(vol.extract_triangle_mesh(), want, "1030 units")
 
 
+TM_GRID = 4096                                            # csrc/gsr_tsdf_mesh.hip: workgroups of the count and the emit at most (test_mesh_cpu holds it to the source)
+ROW_UNITS, ROW_FIELDS = 4100, (0, 1, 4095, 4096, 4099)
+
+
+def _row_volume(fields, order, step=512):
+    """The row of ROW_UNITS units in a pool of 8192, inserted in the given order, `step` units per merge: the fillers are never all on the host."""
+    from gsrast.tsdf import ScalableTSDFVolume
+    vol = ScalableTSDFVolume(VL, 5 * VL, capacity_units=8192)
+    for ch in vol.chunks:
+        ch.fill_(float("nan"))
+    vol.mask.fill_(-1)
+    for i in range(0, len(order), step):
+        vol.merge_units_(*(torch.from_numpy(a).cuda() for a in ref.row_units(fields, order[i:i + step])), assume_unique=True)
+    return vol
+
+
+def test_more_than_4096_units():
+    """4100 units in a row along x: the count and the emit run TM_GRID = 4096 workgroups, and workgroups 0 .. 3 stage a second unit -- output
+    positions 4096 .. 4099 -- into the shared memory that held their first.  A random field in the units at positions 0, 1, 4095, 4096 and 4099 --
+    either side of the grid's turn and at both ends; fillers elsewhere, inserted in a shuffled order.  The truth is the mesh of units 0 .. 3
+    followed by the mesh of units 4092 .. 4099: every unit between is a filler among fillers (test_mesh_cpu holds the identity on 12 units)."""
+    rng = np.random.default_rng(17)
+    n = ROW_UNITS
+    fields = {u: ref.field_unit(rng) for u in ROW_FIELDS}
+    want = ref.concat([ref.extract_row(fields, 0, 4, VL), ref.extract_row(fields, n - 8, n, VL)])
+    past_the_turn = want[0][:, 0] > VL * 16 * TM_GRID                                          # vertices of the units a workgroup takes second
+    assert past_the_turn.sum() > 1000 and (~past_the_turn).sum() > 1000
+    vol = _row_volume(fields, rng.permutation(n))
+    assert vol.num_units == n == 4100 > TM_GRID == 4096
+    mesh = vol.extract_triangle_mesh()
+    _check(mesh, want, "4100 units")
+    assert (mesh.vertices[:, 0] > VL * 16 * TM_GRID).sum().item() == past_the_turn.sum()
+    assert _same_bytes(mesh, vol.extract_triangle_mesh())
+    del vol
+    assert _same_bytes(mesh, _row_volume(fields, rng.permutation(n)).extract_triangle_mesh())   # the same content in another order
+
+
 def test_sphere_on_the_device():
     n, h, centre, r = 32, 0.05, (0.8131, 0.7877, 0.8023), 0.41
     tsdf, w, col = ref.sphere(n, h, centre, r)

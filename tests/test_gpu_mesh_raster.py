@@ -6,7 +6,7 @@ and rint in float64 on widened float32 inputs and one rounding to float32, all I
 test_gpu_smooth.test_filter_smooth_simple_is_bit_equal_to_the_truth already asserts bytes on this device.  Every comparison prints the number of
 components that are not bit-equal first.
 
-Observed on an MI355X: every count printed is 0 -- all maps of all 22 named cases are bit-equal to the truth."""
+Observed on an MI355X: every count printed is 0 -- all maps of all 23 named cases are bit-equal to the truth."""
 import numpy as np
 import pytest
 import torch
@@ -100,6 +100,36 @@ def test_eight_views_equal_eight_calls_and_a_second_run_gives_the_same_bytes():
             assert a[0].cpu().numpy().tobytes() == b[i].cpu().numpy().tobytes(), i
     assert mesh.vertices.cpu().numpy().tobytes() == k["v"].tobytes() and mesh.triangles.cpu().numpy().tobytes() == k["t"].tobytes()
     assert mesh.vertex_colors.cpu().numpy().tobytes() == k["c"].tobytes()
+
+
+def test_1030_views_equal_the_calls_on_the_first_1024_and_the_last_6():
+    """More views than a chunk takes (test_raster_cpu holds the rule): the second turn offsets the matrices, the maps and `dropped` by 1024 views,
+    clears the key buffer, the lists and the owner bytes again and adds its views to the counts.  test_against_the_truth holds the case's maps,
+    `dropped` and counts to the truth; here the whole call against the two calls either side of the chunk edge, the cull, and a second run."""
+    import gsrast
+    name = "box_1030_views"
+    k = cases.CASES[name]
+    cut, n = cases.CHUNK_MAX, len(k["mats"])
+    assert n == 1030 > cut == 1024
+    mesh = _mesh(k)
+    whole = _raster(k, mesh)
+    assert whole.triangle_id.cpu().numpy()[cut:].tobytes() == cases.truth_maps(name)[1][cut:].tobytes() and int((whole.triangle_id[cut:] >= 0).sum()) > 6 * 20
+    first, last = _raster(k, mesh, mats=k["mats"][:cut]), _raster(k, mesh, mats=k["mats"][cut:])
+    assert tuple(last.depth.shape) == (n - cut, k["H"], k["W"])
+    for a, b, c in zip(_bytes(whole), _bytes(first), _bytes(last)):
+        assert a == b + c
+    assert _bytes(_raster(k, mesh)) == _bytes(whole)
+    for tol in (None, cases.TOLERANCE):
+        counts = _counts(k, tol, mesh).cpu().numpy()
+        parts = [gsrast.triangle_view_counts(mesh, _dev(m), k["W"], k["H"], near=k["near"], cull_sign=k["cull_sign"], depth_tolerance=tol).cpu().numpy()
+                 for m in (k["mats"][:cut], k["mats"][cut:])]
+        assert parts[1].max() > 0 and counts.tobytes() == (parts[0] + parts[1]).tobytes() and np.array_equal(counts, cases.truth_counts(name, tol)), tol
+        assert _counts(k, tol, mesh).cpu().numpy().tobytes() == counts.tobytes()
+    want_counts = cases.truth_counts(name, cases.TOLERANCE)
+    out, counts = gsrast.cull_unseen_triangles(mesh, _dev(k["mats"]), k["W"], k["H"], min_views=1000, depth_tolerance=cases.TOLERANCE, near=k["near"], return_counts=True)
+    v, c, t = truth.cull(k["v"], k["c"], k["t"], want_counts, 1000)
+    assert np.array_equal(counts.cpu().numpy(), want_counts) and 0 < len(t) < len(k["t"])
+    assert np.array_equal(out.triangles.cpu().numpy(), t) and out.vertices.cpu().numpy().tobytes() == v.tobytes() and out.vertex_colors.cpu().numpy().tobytes() == c.tobytes()
 
 
 def test_input_layout():

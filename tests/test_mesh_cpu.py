@@ -78,6 +78,37 @@ def test_reference_does_not_depend_on_the_array_cut():
         assert x.tobytes() == y.tobytes()
 
 
+def test_a_row_cut_inside_a_run_of_fillers_gives_two_independent_meshes():
+    """What the 4100-unit GPU test builds its truth on.  A filler unit (tsdf 0.5, weight 1) has no sign change inside it or against another filler, so
+    no vertex and no triangle lies in a cube between two fillers: the mesh of the row is the mesh of the units up to a cut inside a run of fillers,
+    followed by the mesh of the units behind a cut further on in the same run (vertices, colours and triangles in unit order; the second part's
+    indices behind the first's).  12 units, field units at 0, 1, 8 and 11; cut after unit 3 and before unit 6."""
+    rng = np.random.default_rng(21)
+    fields = {u: ref.field_unit(rng) for u in (0, 1, 8, 11)}
+    whole = ref.extract_row(fields, 0, 12, 0.02)
+    first, second = ref.extract_row(fields, 0, 4, 0.02), ref.extract_row(fields, 6, 12, 0.02)
+    assert len(first[2]) > 5000 and len(second[2]) > 5000 and second[0][:, 0].min() > 0.02 * 16 * 7 - 0.02 > first[0][:, 0].max()
+    assert (whole[0][:, 0] > 0.02 * 16 * 2).any() and (second[0][:, 0] < 0.02 * 16 * 8).any()      # a surface inside the fillers next to a field unit
+    for got, want in zip(ref.concat([first, second]), whole):
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+    again = ref.concat([first, ref.extract_row(fields, 4, 12, 0.02)])                         # wherever the run is cut
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, whole))
+    # a cut next to a field unit is NOT free: the cubes across it are lost
+    assert len(ref.concat([ref.extract_row(fields, 0, 8, 0.02), ref.extract_row(fields, 8, 12, 0.02)])[2]) < len(whole[2])
+
+
+def test_the_grid_of_the_mesh_kernels_is_capped_at_4096_units():
+    """k_tm_count and k_tm_emit run min(n_units, TM_GRID) workgroups that walk k = blockIdx.x, += gridDim.x: a workgroup stages a second unit only
+    past TM_GRID units, which test_gpu_mesh.test_more_than_4096_units crosses with 4100."""
+    import test_gpu_mesh as G
+    src = open(os.path.join(ROOT, "gs-sr_amd", "csrc", "gsr_tsdf_mesh.hip")).read()
+    assert re.search(r"^#define TM_GRID %d\s" % G.TM_GRID, src, flags=re.M)
+    assert len(re.findall(r"for \(int k = blockIdx\.x; k < a\.n; k \+= gridDim\.x\)", src)) == 2
+    assert len(re.findall(r"dim3\(\(uint32_t\)std::min\(n_units, TM_GRID\)\)", src)) == 2
+    assert G.ROW_UNITS > G.TM_GRID and all(0 <= u < G.ROW_UNITS for u in G.ROW_FIELDS)
+    assert {G.TM_GRID - 1, G.TM_GRID, 0, G.ROW_UNITS - 1} <= set(G.ROW_FIELDS)                 # either side of the turn and both ends
+
+
 def test_ply_triangle_mesh_round_trip(tmp_path):
     from gsrast import ply
     from gsrast.tsdf import TriangleMesh

@@ -89,6 +89,45 @@ def test_the_cases_hit_what_they_claim():
             truth.rasterize(k["v"], k["t"], k["mats"][0], k["W"], k["H"])
 
 
+def test_the_many_views_case_takes_a_second_chunk_of_views():
+    """gsr_mesh_rasterize walks the views in chunks of min(max(RS_BUDGET / per-view scratch, 1), RS_CHUNK_MAX, n_views) and its scratch is one
+    chunk's: the library's own answer stops growing at RS_CHUNK_MAX views for this size, so view 1024 of box_1030_views starts a second turn."""
+    import os
+    import re
+    import gsrast
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gs-sr_amd", "csrc", "gsr_mesh_raster.hip")).read()
+    assert re.search(r"^#define RS_CHUNK_MAX %d\s" % cases.CHUNK_MAX, src, flags=re.M) and re.search(r"^#define RS_BUDGET \(\(size_t\)256 << 20\)", src, flags=re.M)
+    assert "for (int64_t v0 = 0; v0 < n_views; v0 += m.chunk)" in src
+    k = cases.CASES["box_1030_views"]
+    n, T, V, W, H = len(k["mats"]), len(k["t"]), len(k["v"]), k["W"], k["H"]
+    assert (n, T, W, H) == (cases.MANY_VIEWS, 12, 16, 12) and n > cases.CHUNK_MAX
+    q = lambda views: gsrast.lib().gsr_mesh_raster_scratch_bytes(T, V, views, W, H)
+    assert q(cases.CHUNK_MAX - 1) < q(cases.CHUNK_MAX) == q(n) == q(100000)                   # the views, not the budget, cap the chunk
+    align = lambda x: -(-x // 256) * 256
+    per_view = align(W * H * 8) + align(4 * T) + align(T)                                    # rs_carve: keys, list and owner bytes of one view
+    assert (256 << 20) // per_view > 100 * cases.CHUNK_MAX and "RS_BUDGET / per_view" in src  # the budget alone would allow a hundred times as many
+    assert q(cases.CHUNK_MAX) - q(cases.CHUNK_MAX // 2) >= (cases.CHUNK_MAX // 2) * (W * H * 8 + 5 * T)
+    # the truth: every view sees the box, and the counts differ from triangle to triangle
+    hits = [int((r["triangle_id"] >= 0).sum()) for r in cases.truth_views("box_1030_views")]
+    assert min(hits) > 20 and all(r["dropped"].tolist() == [0, 0, 0] for r in cases.truth_views("box_1030_views"))
+    plain, tol = cases.truth_counts("box_1030_views"), cases.truth_counts("box_1030_views", cases.TOLERANCE)
+    assert plain.sum() > 2 * n and (tol >= plain).all() and tol.max() <= n and len(set(tol.tolist())) > 1 and tol.min() < 1000 <= tol.max()
+    both = lambda a, b: truth.view_counts(k["v"], k["t"], k["mats"][a:b], W, H, k["near"], k["cull_sign"], cases.TOLERANCE, views=cases.truth_views("box_1030_views")[a:b])
+    assert np.array_equal(both(0, cases.CHUNK_MAX) + both(cases.CHUNK_MAX, n), tol) and both(cases.CHUNK_MAX, n).max() > 0
+
+
+def test_the_scratch_query_refuses_what_the_input_check_cannot_cover():
+    """k_rs_check runs one thread per vertex component and index, 3 max(V, T) of them in 32-bit arithmetic: V is held to 3 V < 2^31 like T, so that
+    the rounded-up grid never wraps and leaves vertices unchecked.  The scratch query answers 0 for a refused size, as for every other one."""
+    import gsrast
+    q = lambda T, V: gsrast.lib().gsr_mesh_raster_scratch_bytes(T, V, 3, 16, 12)
+    last = (1 << 31) // 3                                  # 3 * 715 827 882 = 2^31 - 2
+    assert 3 * last < 1 << 31 <= 3 * (last + 1)
+    assert q(10, last) > 0 and q(last, last) > 0 and q(last, 10) > 0
+    assert q(10, last + 1) == 0 and q(10, (1 << 31) - 1) == 0 and q(10, 1431655681) == 0 and q(last + 1, 10) == 0 and q(10, -1) == 0
+    assert q(10, last) == q(10, 10)                        # the vertices take no scratch
+
+
 def _ray_cast(k, M):
     """An independent float64 ray cast on the UNSNAPPED coordinates: strict inequalities, no tie rule, no integers.  -> ids [H,W] (-1: no hit),
     and the mask of the pixels that are more than 4/256 px from the (infinite) edge lines of every triangle in front of the near plane (snapping

@@ -316,7 +316,10 @@ def test_library_exports_the_entry_points_and_the_abi_stays_8():
 def test_scratch_queries_refuse_what_the_kernels_cannot_index():
     import gsrast
     L = gsrast.lib()
-    last_T, last_V = (1 << 31) // 3, (1 << 31) - 1         # 3T = 2^31 - 2 and V = 2^31 - 1 are the last sizes that fit
+    # V = 2^31 - 1 and 6T = 2^32 - 4096 are the last sizes that fit: the 6T pairs go through grids and block counts that round their number up by as
+    # much as 4096 (the sort's largest block) in 32-bit arithmetic, and from 6T = 2^32 - 4095 on that sum wraps -- 3T < 2^31 alone let 682 sizes through
+    last_T, last_V = ((1 << 32) - 4096) // 6, (1 << 31) - 1
+    assert 6 * last_T + 4095 < 1 << 32 <= 6 * (last_T + 1) + 4095 and 3 * (last_T + 1) < 1 << 31
     for q in (L.gsr_mesh_adjacency_scratch_bytes, L.gsr_mesh_normals_scratch_bytes, lambda T, V: L.gsr_mesh_smooth_scratch_bytes(T, V, 0),
               lambda T, V: L.gsr_mesh_smooth_scratch_bytes(T, V, 1)):
         assert q(0, 0) > 0 and q(1000, 600) > q(10, 600) > 0
