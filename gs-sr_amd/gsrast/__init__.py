@@ -205,3 +205,5 @@ from .chamfer import NearestGrid  # noqa: E402,F401
 from . import register  # noqa: E402,F401
 from .register import transform_points, correspondence_sums, solve_transform, fit_transform, icp, evaluate_registration, crop_polygon_volume  # noqa: E402,F401
 from .register import RegistrationResult  # noqa: E402,F401
+from . import images  # noqa: E402,F401
+from .images import resize_u8, pil_to_torch, camera_images, load_resolution, PILtoTorch, load_camera_images  # noqa: E402,F401

@@ -245,6 +245,8 @@ FUNCTIONS = [
     ("gsr_icp", cint, [vp, i64, vp, i64, f32, P(f64), i32, f64, f64, i32, vp, vp, sz, vp]),
     ("gsr_crop_polygon_scratch_bytes", sz, []),
     ("gsr_crop_polygon_volume", cint, [vp, i64, P(f64), i32, i32, f64, f64, vp, vp, sz, vp]),
+    ("gsr_image_resample_scratch_bytes", sz, [i32, i32, i32, i32, i32]),
+    ("gsr_image_resample", cint, [vp, i32, i32, i32, i64, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
     ("gsr_debug_read", cint, [_cfg, i32, vp, vp, sz, vp, u32, vp, vp]),
     ("gsr_profile_enable", cint, [i32]),
     ("gsr_profile_read", cint, [P(f64), P(u64)]),

@@ -1058,6 +1058,43 @@ size_t gsr_crop_polygon_scratch_bytes(void);
 int gsr_crop_polygon_volume(const float* points /*[N,3]*/, int64_t n_points, const double* polygon /*host [K,2]*/, int32_t n_polygon, int32_t axis, double axis_min,
                             double axis_max, uint8_t* keep /*[N]*/, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- image preparation: a training photograph brought to its training size and into the tensors a camera holds (PILtoTorch,
+ * gssr/utils/general_utils.py:21-27; Camera.__init__, gssr/cameras/__init__.py:59-77; additions, no ABI bump).  Pillow's 8-bit resampler is an integer
+ * algorithm over a float64 coefficient table: the result is DEFINED as the bytes of PIL.Image.resize((W, H)) with its defaults (bicubic, no box, no
+ * reducing_gap) and held to a restatement of the following, operation by operation (tests/images_truth.py).
+ * image: uint8 [h, w, C], interleaved, row r at image + r * row_stride bytes, row_stride >= w * C; C = 1 (mode L), 3 (RGB) or 4 (RGBA).  Rows of C = 1 and 3
+ *   start at any byte; for C = 4 a pixel is one dword: image and row_stride are multiples of 4.  Limits: 1 <= w, h, W, H, h * w * C < 2^31 and
+ *   H * W * C < 2^31.
+ * An axis of input size `in` and output size `out`, everything in double and every operation rounded on its own:
+ *     scale = in / out,  fs = max(scale, 1),  support = 2 * fs,  ss = 1 / fs;
+ *     output index xx:  center = (xx + 0.5) * scale,  xmin = max((int)(center - support + 0.5), 0),  xmax = min((int)(center + support + 0.5), in),
+ *       n = xmax - xmin,  w_x = f(((x + xmin) - center + 0.5) * ss) for x < n;
+ *     f(t), t = |t|:  ((1.5 * t - 2.5) * t * t + 1 for t < 1,  (((t - 5) * t + 8) * t - 4) * -0.5 for t < 2,  else 0;
+ *     ww = the sum of the w_x in ascending x from 0;  where ww != 0:  w_x = w_x / ww;
+ *     k_x = (int)(w_x * 2^22 + 0.5) for w_x >= 0, else (int)(w_x * 2^22 - 0.5): both truncate toward zero.
+ *   A pass: out = clip8(((1 << 21) + sum of k_x * pixel[xmin + x]) >> 22), a signed 32-bit sum, an arithmetic shift, clip8 clamps to [0, 255].
+ *   The horizontal pass (only where W != w) is rounded to uint8, the vertical pass (only where H != h) runs on its result.  An axis that does not run
+ *   is evaluated here as the one tap k = 2^22 at xmin = xx, which gives the same bytes.
+ * C = 4, unless (W, H) == (w, h): colours are premultiplied first, t = c * a + 128, c' = ((t >> 8) + t) >> 8, alpha is resampled as it is, and colours
+ *   are un-premultiplied last: as they are where the resampled alpha is 0 or 255, else min((255 * c) / a, 255) with integer division.
+ *   (W, H) == (w, h): the result is a copy.
+ * Outputs, each of them nullable, from the resampled bytes v of a pixel, q_c = (float)v_c / 255.0f, the correctly rounded float32 quotient (what
+ *   torch.from_numpy(u8) / 255.0 gives on the host; a product with the float32 reciprocal differs in 126 of the 256 values):
+ *     out_u8     uint8 [H, W, C], interleaved and packed: v;
+ *     out_planes float [n_planes, H, W], n_planes <= C: plane c = q_c -- times q_3 for c < 3 where out_mask is given;
+ *     out_gray   float [H, W], C >= 3: (0.2989f * q_0 + 0.587f * q_1) + 0.114f * q_2, three products and two sums, each rounded (torchvision's
+ *                Grayscale on the clamped image, taken BEFORE the mask is applied, as Camera.__init__ line 64 does);
+ *     out_mask   float [H, W], C == 4 and n_planes <= 3: q_3.
+ * Three launches (the two coefficient tables, the horizontal pass, the vertical pass with the outputs), no host synchronisation, no atomics.  The
+ * tables and the intermediate image live in the scratch: caller-owned, 16-byte aligned, gsr_image_resample_scratch_bytes() bytes (0: sizes out of range).
+ * GSR_IMG_HSTRIP / GSR_IMG_VSTRIP: output columns per workgroup of the horizontal / vertical pass (csrc/gsr_image.hip). */
+#define GSR_IMG_HSTRIP 256
+#define GSR_IMG_VSTRIP 256
+size_t gsr_image_resample_scratch_bytes(int32_t w, int32_t h, int32_t C, int32_t W, int32_t H);
+int gsr_image_resample(const uint8_t* image /*[h,w,C]*/, int32_t w, int32_t h, int32_t C, int64_t row_stride, int32_t W, int32_t H, uint8_t* out_u8 /*[H,W,C] or NULL*/,
+                       float* out_planes /*[n_planes,H,W] or NULL*/, int32_t n_planes, float* out_gray /*[H,W] or NULL*/, float* out_mask /*[H,W] or NULL*/,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- introspection for parity tests (copies a private stage result into a caller DEVICE buffer) */
 enum gsr_debug_field {
     GSR_DBG_TILES_TOUCHED = 0, /* uint32 [P]                                      (from geom)    */
